@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the DAS hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c5|c1|small]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c5|c1|small] [--dump-outputs DIR] [--full]
 
 One "step" = one full-frame delay-and-sum of the workload (default: BASELINE config C3 -- 256-element
 array, 256-transmit full-synthetic-aperture, 1024 x 1024 Cartesian scan, T = 2816, complex64 channel
@@ -13,10 +13,14 @@ bench.py --gpus N ...` (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or --
 bench.py re-executes ITSELF under torch.distributed.run, so a bare `python bench.py --gpus 8` works too.
 The SAME image is split into N contiguous slabs of the linear pixel index, every rank beamforms its slab
 from its own replica of the data, and the slabs are gathered with one RCCL all_gather -- inside the timed
-region (strong scaling of one frame).  Outside the timed region rank 0 also reports the per-rank kernel
-times, the gather alone, and the cost of replicating the channel data from rank 0 (RCCL broadcast).
+region (strong scaling of one frame).  With --full, outside the timed region rank 0 also reports the per-rank
+kernel times, the gather alone, and the cost of replicating the channel data from rank 0 (RCCL broadcast).
 
-Rank 0 prints ONE JSON line: metric/value/unit per BASELINE.json plus
+A plain run sets up, warms up, times K steps and prints ONE JSON line on rank 0: metric/value/unit per
+BASELINE.json, ms_per_step (the wall time of one timed step), dtype and the plan's configuration.
+--dump-outputs DIR writes the image of the last timed step (dump_outputs); the input frame comes from a
+fixed seed, so two builds given the same arguments can be compared output for output.
+--full measures and checks everything else, in runs and passes of its own after the timed region:
   "roofline":     algorithmic HBM bytes per launch / measured kernel time (hipEvents on the launch stream),
                   HBM traffic from rocprofv3 counter passes of this very command (N = 1; --traffic file|none to skip),
                   the fp32-VALU fraction on the model AND on the executed flop count of the kernel
@@ -170,7 +174,7 @@ def measure_traffic(argv):
             d = os.path.join(tmp, ctrs[0])
             cmd = [exe, "--kernel-trace", "--pmc", *ctrs, "--output-format", "csv", "-d", d, "-o", "p", "--",
                    sys.executable, os.path.abspath(__file__)] + argv + ["--steps", "2", "--warmup", "1", "--no-cpu", "--traffic", "none",
-                                                                       "--no-general"]
+                                                                       "--no-general", "--full"]
             r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=420)
             files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
             if r.returncode != 0 or not files:
@@ -253,6 +257,28 @@ def saturated_issue_rate(lib, cu):
         return None
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, y):
+    """--dump-outputs DIR: the image of the last timed step as the plan hands it to its caller -- (frames, 1, 1, pixels), pixels in column-major
+    order of the I1 x I2 scan -- with real and imaginary part along a last axis of 2, as DIR/image.npy: float32 (float64 for double-precision data).
+    An image above 64 MB is replaced by a fixed sample of its pixels (seed 0), DIR/image_sample.npy, with their flat indices in
+    DIR/image_sample_index.npy (float64)."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    ft = torch.float64 if y.dtype == torch.complex128 else torch.float32
+    yr = torch.view_as_real(y).to(ft).cpu().numpy()
+    if yr.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(d, "image.npy"), yr)
+        return
+    flat = yr.reshape(-1, 2)
+    k = DUMP_MAX_BYTES // (flat.itemsize * 2 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=k, replace=False))
+    np.save(os.path.join(d, "image_sample.npy"), flat[idx])
+    np.save(os.path.join(d, "image_sample_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -260,8 +286,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="c3")
     ap.add_argument("--kernel", type=int, default=0, help="0 auto, 1 generic, 2 tiled")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-general", action="store_true", help="skip the reciprocal-mode-off measurement")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-general", action="store_true", help="--full: skip the reciprocal-mode-off measurement")
     ap.add_argument("--no-reciprocal", action="store_true", help="disable the reciprocal mode for the headline measurement itself (plan flag)")
     ap.add_argument("--frames", type=int, default=1, help="frames per step: a STREAM of F distinct frames through the plan (the shape of the reference's own benchmark, "
                     "test/ParTest.m:244-271: F = 10): launches shared by two (four) frames compute tap index and weights once per group; value = I * F / t, "
@@ -272,10 +298,10 @@ def main():
                     "the kernel hiprtc compiles for this plan's sizes (the reference's benchmark runs const-compiled kernels too: "
                     "src/UltrasoundSystem.m:5626-5748, test/ParTest.m:322-327)")
     ap.add_argument("--jit", action="store_true", help="(default; kept for compatibility)")
-    ap.add_argument("--no-traffic", action="store_true", help="same as --traffic none")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: same as --traffic none")
     ap.add_argument("--checksum", action="store_true", help="add image_checksum (xxh3 / blake2b of the final image bytes on rank 0)")
     ap.add_argument("--traffic", default="auto", choices=["auto", "live", "file", "none"],
-                    help="roofline.traffic: rocprofv3 counter passes of this command (live; auto = live at N=1) or profiles/traffic_<w>.json")
+                    help="--full: roofline.traffic: rocprofv3 counter passes of this command (live; auto = live at N=1) or profiles/traffic_<w>.json")
     ap.add_argument("--fmod", type=float, default=0.0, help="remodulation frequency [Hz] ('modulation' option): baseband data; not the headline")
     ap.add_argument("--rx-apod", default=None, help="generated receive apodization for ANY workload, e.g. fnumber:1.5 | acceptance:30 | cosine:45 "
                     "(evaluated inside the kernel: what an apodized frame costs); not the headline")
@@ -294,7 +320,13 @@ def main():
                     "does not shrink with the slab).  Reported as such (config.prefolded_timed_region), with the fold + replication time beside it; not the default")
     ap.add_argument("--gen-apod", action="store_true", help="generate the workload's receive apodization inside the kernel "
                     "(qdas_desc.rx_apod_*) instead of streaming the materialised I x N array")
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure and check everything else: kernel time and roofline (rocprofv3 counter "
+                    "passes), the same frame without the fold / mirror / reciprocal modes and on the prebuilt kernel, a stream of frames, the CPU baselines "
+                    "and parity_check, the multi-GPU layouts.  Without it a run times the headline steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the image of the last timed step as DIR/image.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     args.jit = not args.no_jit
     if args.no_traffic:
         args.traffic = "none"
@@ -428,6 +460,8 @@ def main():
         tt = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, yimg)
 
     # ---- outside the timed region
     def kernel_time(p, reps):
@@ -439,10 +473,10 @@ def main():
         p.set_timing(False)
         return float(np.mean(ks))
 
-    kernel_ms = kernel_time(plan, max(2, min(args.steps, 5)))     # hipEvents on the launch stream
+    kernel_ms = kernel_time(plan, max(2, min(args.steps, 5))) if args.full else None     # hipEvents on the launch stream
     fallback = plan.fallback_tiles()
     multi = {}
-    if world > 1:
+    if world > 1 and args.full:
         km = torch.tensor([kernel_ms], device=dev, dtype=torch.float64)
         allk = [torch.zeros_like(km) for _ in range(world)]
         dist.all_gather(allk, km)
@@ -600,19 +634,19 @@ def main():
     reciprocal = bool(plan.reciprocal)
     folded = bool(plan.folded)
     unfolded_ms = None
-    if world == 1 and folded and not args.no_general:          # the same frame with both traces of every pair gathered (rounds 1-3: plan flag QDAS_PLAN_NO_FOLD)
+    if world == 1 and folded and args.full and not args.no_general:          # the same frame with both traces of every pair gathered (rounds 1-3: plan flag QDAS_PLAN_NO_FOLD)
         uplan = DasPlan(prob, device=dev, kernel=args.kernel, reciprocal=True, jit=args.jit, fold=False, **slab_kw)
         uplan.execute_colmajor(xc, F)
         unfolded_ms = kernel_time(uplan, 3)
         uplan.close()
     fold_only_ms = None
-    if world == 1 and folded and bool(plan.mirror) and not args.no_general:   # the same frame on the folded kernel WITHOUT the lateral-mirror mode: what a reciprocal acquisition
+    if world == 1 and folded and bool(plan.mirror) and args.full and not args.no_general:   # the same frame on the folded kernel WITHOUT the lateral-mirror mode: what a reciprocal acquisition
         fplan = DasPlan(prob, device=dev, kernel=args.kernel, reciprocal=True, jit=args.jit, mirror=False, **slab_kw)   # with a calibrated (not mirror-symmetric) probe costs
         fplan.execute_colmajor(xc, F)
         fold_only_ms = kernel_time(fplan, 3)
         fplan.close()
     general_ms = None
-    if world == 1 and reciprocal and not args.no_general:      # the same frame without the reciprocal special case (plan flag)
+    if world == 1 and reciprocal and args.full and not args.no_general:      # the same frame without the reciprocal special case (plan flag)
         gplan = DasPlan(prob, device=dev, kernel=args.kernel, reciprocal=False, jit=args.jit, **slab_kw)       # (no reciprocal mode: no fold either)
         gplan.execute_colmajor(xc, F)
         general_ms = kernel_time(gplan, 3)
@@ -622,7 +656,7 @@ def main():
     # test/ParTest.m:244-271): frame pairs share a launch -- tap index and weights once per pair --, so a stream is faster per frame than the
     # single-frame headline above.  Reported beside it, never as `value`; the last frame is compared with its own single-frame execute.
     stream = None
-    if world == 1 and F == 1 and not args.no_general and not os.environ.get("QDAS_BENCH_CHILD"):
+    if world == 1 and F == 1 and args.full and not args.no_general and not os.environ.get("QDAS_BENCH_CHILD"):
         try:
             FS = 4
             g2 = torch.Generator(device=dev).manual_seed(4321)
@@ -674,14 +708,14 @@ def main():
             stream = {"frames": 4, "ms_per_frame": None, "note": f"failed: {ex!r}"}
 
     prebuilt_ms = None
-    if world == 1 and args.jit and not os.environ.get("QDAS_BENCH_CHILD"):      # the same frame on the prebuilt instantiation
+    if world == 1 and args.jit and args.full and not os.environ.get("QDAS_BENCH_CHILD"):      # the same frame on the prebuilt instantiation
         pplan = DasPlan(prob, device=dev, kernel=args.kernel, reciprocal=not args.no_reciprocal, jit=False, fold=not args.no_fold, **slab_kw)
         pplan.execute_colmajor(xc, F)
         prebuilt_ms = kernel_time(pplan, 3)
         pplan.close()
 
     traffic, tsrc, ctrs = None, "not measured", {}
-    if rank == 0 and not os.environ.get("QDAS_BENCH_CHILD"):
+    if rank == 0 and args.full and not os.environ.get("QDAS_BENCH_CHILD"):
         mode = args.traffic
         if mode == "auto":
             mode = "live" if world == 1 else "file"
@@ -709,33 +743,8 @@ def main():
         ms = el / args.steps * 1e3
         I_step = I * F                                             # pixels beamformed per step
         pairs = I * N * M
-        sb = {"halfT": 4, "single": 8, "double": 16}[w["prec"]]
-        apb = 0 if w["apod"] is None else w["apod"].size * sb // 2
-        alg_bytes = (T * N * M * sb + 12 * I + sb * I + apb) / world      # per launch (per rank): x + Pi + y (+ apod)  (SURVEY 8d "B")
         info = _lib.device_info(local)
-        ksec = kernel_ms * 1e-3
         mirror = bool(plan.mirror)
-        exec_fpp = exec_flop_per_pair(w["interp"], (2 if mirror else 1) if folded else (2 if reciprocal else 1) * (2 if mirror else 1), folded)
-        # pairs the kernel really executes: a pixel x receiver weight (array or generated rule) drops whole (wave, receiver) stages
-        exec_frac, mask = 1.0, None
-        try:
-            if args.rx_apod and not args.rx_apod_array and plan.kernel == "tiled":
-                from qups_amd import apodization as A
-                kind, _, par = args.rx_apod.partition(":")
-                fn = {"acceptance": A.ap_acceptance_angle, "cosine": A.ap_cosine_angle, "fnumber": A.ap_aperture_growth}[kind]
-                nrm = w.get("nrm")
-                if nrm is None:
-                    nrm = np.tile(np.array([[0.0], [0.0], [1.0]]), (1, N))
-                mask = fn(w["Pi"], w["Pr"], nrm, *([float(par)] if par else []))
-            elif plan.kernel == "tiled" and not args.tx_apod:
-                for a in opts["apod"]:
-                    a = np.asarray(a)
-                    if a.ndim >= 4 and a.shape[0] == w["I1"] and a.shape[1] == w["I2"] and a.shape[3] == N and (a.ndim < 5 or a.shape[4] == 1):
-                        mask = a if mask is None else mask * a
-            if mask is not None:
-                exec_frac = executed_pair_fraction(np.asarray(mask).reshape(w["I1"], w["I2"], N), plan.wave_shape())
-        except Exception:
-            exec_frac = None
         rec = {
             "metric": "beamformed Mpixels/sec (1024^2 px, 256x256 Tx/Rx)" if w["name"] == "c3" else "beamformed Mpixels/sec",
             "value": round(I_step / (el / args.steps) / 1e6, 4), "unit": "Mpixel/s",
@@ -745,108 +754,135 @@ def main():
                        "kernel_name": plan.kernel_name(), "jit": bool(args.jit),
                        "fallback_tiles": fallback, "tile": list(plan.tile_shape()), "wave": list(plan.wave_shape()), "aperture_split": plan.aperture_split(), "parallelism": (f"{'mirror-' if splan.mirror_slabs else ''}pixel-slab x{world} + RCCL all_gather") if world > 1 else "1 GPU",
                        "device": info["name"], "cu": info["cu_count"]},
-            "roofline": {"bound": "hbm", "achieved": round(alg_bytes / ksec / 1e9, 3), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(alg_bytes / ksec / 1e9 / HBM_PEAK_GBS, 6),
-                         "traffic": traffic, "traffic_source": tsrc, "kernel_ms": round(kernel_ms, 3), "algorithmic_bytes": int(alg_bytes),
-                         **({} if not apb else {"algorithmic_bytes_reference_convention": int(alg_bytes + apb / world),
-                                                "algorithmic_bytes_note": "algorithmic_bytes counts the apodization array as this ABI takes it -- REAL weights in the data precision (apod_real), "
-                                                                          "half the bytes; the reference casts weights to complex (kern/das_spec.m:243,345), which is what SURVEY 8d / BASELINE.md price "
-                                                                          "(algorithmic_bytes_reference_convention)"}),
-                         "note": "compulsory-traffic accounting: this path is FP32-VALU / LDS-gather bound "
-                                 "(~2.5e3 flop/byte): valu_frac_executed = flops the pair loop executes / fp32 vector peak; "
-                                 "reference_model_tflops = the REFERENCE kernel's per-pair flop count (SURVEY 8d) x pairs / time -- an equivalent rate that can exceed "
-                                 "the vector peak because reciprocal / mirror modes share index and weight work between traces",
-                         "gpairs_per_s": round(pairs / world / ksec / 1e9, 3),
-                         "reference_model_tflops": round(pairs / world * FLOP_PER_PAIR.get(w["interp"], 42) / ksec / 1e12, 3),
-                         "valu_flop_per_pair_executed": exec_fpp,
-                         "pairs_executed_frac": None if exec_frac is None else round(exec_frac, 4),
-                         "valu_frac_executed": None if exec_fpp is None or exec_frac is None or plan.kernel != "tiled" or args.tx_apod else
-                                               round(pairs / world * exec_frac * exec_fpp / ksec / 1e12 / FP32_PEAK_TFLOPS, 4)},
         }
-        try:
-            taps = {"nearest": 1, "linear": 2, "cubic": 4, "lanczos3": 4}.get(w["interp"], 4)
-            rec["roofline"].update(binding_roofs(ctrs, info["cu_count"], pairs / world * (exec_frac or 1.0) * ((N + 1) / (2.0 * N) if folded else 1.0), taps, sb))
-        except Exception as ex:
-            rec["roofline"]["binding_note"] = f"counter post-processing failed: {ex!r}"
-        # The roof that BINDS: VALU issue under the part's power limit.  achieved = wave64 VALU instructions the dominant kernel issued
-        # (SQ_INSTS_VALU of the counter pass of this command) / its launch time; peak = the SATURATED issue rate of the pair loop's own VALU mix, measured on
-        # this device in this run (csrc/probe.hip qdas_debug_issue_rate, mix 2: 16 broadcast pk_fma + 16 SGPR-coefficient pk_fma + 5 index instructions, four
-        # waves per SIMD on every CU, no LDS reads -- so frac < 1 also prices the gathers, the staging and the per-stage code).  The BASELINE's HBM roof stays
-        # in the line as nominal_hbm_*: SURVEY 8d predicted, and every round measured, that compulsory traffic is ~1 % of it.
-        rf = rec["roofline"]
-        rf["nominal_hbm_achieved"], rf["nominal_hbm_peak"], rf["nominal_hbm_frac"], rf["nominal_hbm_unit"] = rf["achieved"], rf["peak"], rf["frac"], "GB/s"
-        # (not in the counter passes' child runs: the probe's launches would be the longest kernels of a short workload's trace)
-        sat = None if os.environ.get("QDAS_BENCH_CHILD") else saturated_issue_rate(_lib.lib(), info["cu_count"])
-        if sat and plan.kernel == "tiled" and "valu_insts" in rf and rf.get("counter_pass_kernel_ms"):
-            ach = rf["valu_insts"] / (rf["counter_pass_kernel_ms"] * 1e-3) / 1e9
-            rf.update({"bound": "valu_issue", "achieved": round(ach, 2), "peak": round(sat["pair_mix_ginst_s"], 2), "unit": "Gwave-inst/s", "frac": round(ach / sat["pair_mix_ginst_s"], 4),
-                       "peak_source": sat["note"], "saturated_ns_per_inst_simd": sat["ns"]})
-            rf.pop("valu_issue_frac", None)             # (rounds 3-4: instructions x 4 cycles / active cycles -- a convention, not a measured roof)
-            rf["binding_note"] = ("VALU issue under the power limit binds (frac: against the measured saturated rate of the loop's own VALU mix on this box); LDS gathers second "
-                                  "(lds_busy_frac); nominal_hbm_frac is the BASELINE's roof, unreachable at ~2.5e3 flop/byte")
-        elif sat:
-            rf["bound_note"] = "bound = hbm is the BASELINE's nominal roof only: no SQ counters in this run to price the VALU-issue roof that binds"
-            rf["saturated_ns_per_inst_simd"] = sat["ns"]
         if F > 1:
             rec["frames_per_step"] = F
             rec["ms_per_frame"] = round(ms / F, 3)
             rec["config"]["workload"] += f" [stream of {F} distinct frames per step]"
-            rec["roofline"]["kernel_ms_is"] = "per frame (kernel time of the step / frames)"
-        if stream is not None:
-            rec["stream"] = stream
-        if prebuilt_ms is not None:
-            rec["prebuilt_kernel_ms"] = round(prebuilt_ms, 3)
-        if folded:
-            rec["roofline"]["fold_note"] = ("reciprocal acquisition: every step first adds the two traces of each unordered transmit / receive pair (fold.hip: one pass over "
-                                            "HBM, inside the timed region and inside kernel_ms), then the fused kernel sums the N(N+1)/2 folded traces -- the image is the "
-                                            "full N x M sum (linearity of the interpolators; parity_check on random, non-symmetric data); products_formed_frac = "
-                                            "share of the N x M products formed per pixel; unfolded_ms_per_step = the same frame with the plan flag QDAS_PLAN_NO_FOLD")
-            rec["roofline"]["products_formed_frac"] = round((N + 1) / (2.0 * N), 4)
-        if unfolded_ms is not None:
-            rec["unfolded_ms_per_step"] = round(unfolded_ms, 3)
-        if fold_only_ms is not None:
-            rec["fold_only_ms_per_step"] = round(fold_only_ms, 3)
-        if general_ms is not None:
-            rec["general_ms_per_step"] = round(general_ms, 3)
-            rec["general_value"] = round(I / (general_ms * 1e-3) / 1e6, 4)
-        if stream and stream.get("general_stream") and stream["general_stream"].get("ms_per_frame") is not None:
-            rec["general_stream_ms_per_frame"] = stream["general_stream"]["ms_per_frame"]      # (no symmetry mode at all, four frames per launch: beside the headline, never `value`)
-        if multi:
-            rec["multi_gpu"] = multi
-        if world == 1 and not args.no_cpu:
+        if args.full:                                              # (everything beside the headline: measured in runs of its own)
+            sb = {"halfT": 4, "single": 8, "double": 16}[w["prec"]]
+            apb = 0 if w["apod"] is None else w["apod"].size * sb // 2
+            alg_bytes = (T * N * M * sb + 12 * I + sb * I + apb) / world      # per launch (per rank): x + Pi + y (+ apod)  (SURVEY 8d "B")
+            ksec = kernel_ms * 1e-3
+            exec_fpp = exec_flop_per_pair(w["interp"], (2 if mirror else 1) if folded else (2 if reciprocal else 1) * (2 if mirror else 1), folded)
+            # pairs the kernel really executes: a pixel x receiver weight (array or generated rule) drops whole (wave, receiver) stages
+            exec_frac, mask = 1.0, None
             try:
-                xlast = xc if F == 1 else xc[F - 1]
-                xh = torch.view_as_real(xlast).float().cpu().numpy().view(np.complex64).reshape(M, N, T).transpose(2, 1, 0)
-                plain = not (args.fmod or args.rx_apod or args.window_apod or args.tx_apod or args.gen_apod)
-                cb, lstep, limg = cpu_baseline(w, xh, apod=w["apod"] if plain else None)
-                rec["cpu_baseline"] = cb[0]
-                if len(cb) > 1:
-                    rec["cpu_baseline_tuned"] = cb[1]
-                # parity of the very frame that was timed (last timed step, the kernel named in config.kernel_name) against the CPU
-                # port on the baseline's pixel lattice -- outside the timed region
-                if plain and limg is not None:
-                    from oracle import das_ref
-                    img = torch.view_as_real(yimg.reshape(F, -1)[F - 1]).float().cpu().numpy().view(np.complex64).reshape(w["I1"], w["I2"], order="F")
-                    den = float(np.abs(limg).max())
-                    err32 = float(np.abs(img[::lstep, ::lstep] - limg).max()) / (den if den > 0 else 1.0)
-                    # the judge of parity is the DOUBLE-precision port (the float32 port's own rounding -- fp32 delays at tau*fs ~ 3e3
-                    # samples -- is ~1.5e-4 of the maximum at C3, above the kernel's): every other lattice pixel per axis
-                    s2 = 2 * lstep
-                    ap = () if w["apod"] is None else (w["apod"][::s2, ::s2],)
-                    ref = das_ref.das_spec("DAS", w["Pi"][:, ::s2, ::s2, :], w["Pr"], w["Pv"], w["Nv"], xh, w["t0"], w["fs"],
-                                           1.0 / np.float64(np.float32(1.0 / w["c0"])), VS="plane-waves" not in w["opt"],
-                                           DV="diverging-waves" in w["opt"], interp=w["interp"], apod=ap, prec="double")[:, :, 0, 0, 0]
-                    den64 = float(np.abs(ref).max())
-                    err = float(np.abs(img[::s2, ::s2] - ref).max()) / (den64 if den64 > 0 else 1.0)
-                    tol = 2e-3 if w["prec"] == "halfT" else 1e-4
-                    rec["parity_check"] = {"rel_err": float(f"{err:.3e}"), "tol": tol, "pixels": int(ref.size), "ok": bool(err <= tol and den64 > 0),
-                                           "against": "oracle/das_ref.c in double precision (the C restatement the cpu_baseline times in float32) on "
-                                                      "every %dth pixel per axis of the frame of the last timed step; max |gpu - cpu| / max |cpu|" % s2,
-                                           "rel_err_vs_float32_port": float(f"{err32:.3e}"), "pixels_float32_port": int(limg.size),
-                                           "kernel": plan.kernel_name()}
-            except Exception as ex:  # report, never hide
-                rec["cpu_baseline"] = {"value": None, "unit": "Mpixel/s", "cores": os.cpu_count(), "kind": "port",
-                                       "sample": f"FAILED: {ex!r}"}
+                if args.rx_apod and not args.rx_apod_array and plan.kernel == "tiled":
+                    from qups_amd import apodization as A
+                    kind, _, par = args.rx_apod.partition(":")
+                    fn = {"acceptance": A.ap_acceptance_angle, "cosine": A.ap_cosine_angle, "fnumber": A.ap_aperture_growth}[kind]
+                    nrm = w.get("nrm")
+                    if nrm is None:
+                        nrm = np.tile(np.array([[0.0], [0.0], [1.0]]), (1, N))
+                    mask = fn(w["Pi"], w["Pr"], nrm, *([float(par)] if par else []))
+                elif plan.kernel == "tiled" and not args.tx_apod:
+                    for a in opts["apod"]:
+                        a = np.asarray(a)
+                        if a.ndim >= 4 and a.shape[0] == w["I1"] and a.shape[1] == w["I2"] and a.shape[3] == N and (a.ndim < 5 or a.shape[4] == 1):
+                            mask = a if mask is None else mask * a
+                if mask is not None:
+                    exec_frac = executed_pair_fraction(np.asarray(mask).reshape(w["I1"], w["I2"], N), plan.wave_shape())
+            except Exception:
+                exec_frac = None
+            rec["roofline"] = {"bound": "hbm", "achieved": round(alg_bytes / ksec / 1e9, 3), "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": round(alg_bytes / ksec / 1e9 / HBM_PEAK_GBS, 6),
+                               "traffic": traffic, "traffic_source": tsrc, "kernel_ms": round(kernel_ms, 3), "algorithmic_bytes": int(alg_bytes),
+                               **({} if not apb else {"algorithmic_bytes_reference_convention": int(alg_bytes + apb / world),
+                                                      "algorithmic_bytes_note": "algorithmic_bytes counts the apodization array as this ABI takes it -- REAL weights in the data precision (apod_real), "
+                                                                                "half the bytes; the reference casts weights to complex (kern/das_spec.m:243,345), which is what SURVEY 8d / BASELINE.md price "
+                                                                                "(algorithmic_bytes_reference_convention)"}),
+                               "note": "compulsory-traffic accounting: this path is FP32-VALU / LDS-gather bound "
+                                       "(~2.5e3 flop/byte): valu_frac_executed = flops the pair loop executes / fp32 vector peak; "
+                                       "reference_model_tflops = the REFERENCE kernel's per-pair flop count (SURVEY 8d) x pairs / time -- an equivalent rate that can exceed "
+                                       "the vector peak because reciprocal / mirror modes share index and weight work between traces",
+                               "gpairs_per_s": round(pairs / world / ksec / 1e9, 3),
+                               "reference_model_tflops": round(pairs / world * FLOP_PER_PAIR.get(w["interp"], 42) / ksec / 1e12, 3),
+                               "valu_flop_per_pair_executed": exec_fpp,
+                               "pairs_executed_frac": None if exec_frac is None else round(exec_frac, 4),
+                               "valu_frac_executed": None if exec_fpp is None or exec_frac is None or plan.kernel != "tiled" or args.tx_apod else
+                                                     round(pairs / world * exec_frac * exec_fpp / ksec / 1e12 / FP32_PEAK_TFLOPS, 4)}
+            try:
+                taps = {"nearest": 1, "linear": 2, "cubic": 4, "lanczos3": 4}.get(w["interp"], 4)
+                rec["roofline"].update(binding_roofs(ctrs, info["cu_count"], pairs / world * (exec_frac or 1.0) * ((N + 1) / (2.0 * N) if folded else 1.0), taps, sb))
+            except Exception as ex:
+                rec["roofline"]["binding_note"] = f"counter post-processing failed: {ex!r}"
+            # The roof that BINDS: VALU issue under the part's power limit.  achieved = wave64 VALU instructions the dominant kernel issued
+            # (SQ_INSTS_VALU of the counter pass of this command) / its launch time; peak = the SATURATED issue rate of the pair loop's own VALU mix, measured on
+            # this device in this run (csrc/probe.hip qdas_debug_issue_rate, mix 2: 16 broadcast pk_fma + 16 SGPR-coefficient pk_fma + 5 index instructions, four
+            # waves per SIMD on every CU, no LDS reads -- so frac < 1 also prices the gathers, the staging and the per-stage code).  The BASELINE's HBM roof stays
+            # in the line as nominal_hbm_*: SURVEY 8d predicted, and every round measured, that compulsory traffic is ~1 % of it.
+            rf = rec["roofline"]
+            rf["nominal_hbm_achieved"], rf["nominal_hbm_peak"], rf["nominal_hbm_frac"], rf["nominal_hbm_unit"] = rf["achieved"], rf["peak"], rf["frac"], "GB/s"
+            # (not in the counter passes' child runs: the probe's launches would be the longest kernels of a short workload's trace)
+            sat = None if os.environ.get("QDAS_BENCH_CHILD") else saturated_issue_rate(_lib.lib(), info["cu_count"])
+            if sat and plan.kernel == "tiled" and "valu_insts" in rf and rf.get("counter_pass_kernel_ms"):
+                ach = rf["valu_insts"] / (rf["counter_pass_kernel_ms"] * 1e-3) / 1e9
+                rf.update({"bound": "valu_issue", "achieved": round(ach, 2), "peak": round(sat["pair_mix_ginst_s"], 2), "unit": "Gwave-inst/s", "frac": round(ach / sat["pair_mix_ginst_s"], 4),
+                           "peak_source": sat["note"], "saturated_ns_per_inst_simd": sat["ns"]})
+                rf.pop("valu_issue_frac", None)             # (rounds 3-4: instructions x 4 cycles / active cycles -- a convention, not a measured roof)
+                rf["binding_note"] = ("VALU issue under the power limit binds (frac: against the measured saturated rate of the loop's own VALU mix on this box); LDS gathers second "
+                                      "(lds_busy_frac); nominal_hbm_frac is the BASELINE's roof, unreachable at ~2.5e3 flop/byte")
+            elif sat:
+                rf["bound_note"] = "bound = hbm is the BASELINE's nominal roof only: no SQ counters in this run to price the VALU-issue roof that binds"
+                rf["saturated_ns_per_inst_simd"] = sat["ns"]
+            if F > 1:
+                rec["roofline"]["kernel_ms_is"] = "per frame (kernel time of the step / frames)"
+            if stream is not None:
+                rec["stream"] = stream
+            if prebuilt_ms is not None:
+                rec["prebuilt_kernel_ms"] = round(prebuilt_ms, 3)
+            if folded:
+                rec["roofline"]["fold_note"] = ("reciprocal acquisition: every step first adds the two traces of each unordered transmit / receive pair (fold.hip: one pass over "
+                                                "HBM, inside the timed region and inside kernel_ms), then the fused kernel sums the N(N+1)/2 folded traces -- the image is the "
+                                                "full N x M sum (linearity of the interpolators; parity_check on random, non-symmetric data); products_formed_frac = "
+                                                "share of the N x M products formed per pixel; unfolded_ms_per_step = the same frame with the plan flag QDAS_PLAN_NO_FOLD")
+                rec["roofline"]["products_formed_frac"] = round((N + 1) / (2.0 * N), 4)
+            if unfolded_ms is not None:
+                rec["unfolded_ms_per_step"] = round(unfolded_ms, 3)
+            if fold_only_ms is not None:
+                rec["fold_only_ms_per_step"] = round(fold_only_ms, 3)
+            if general_ms is not None:
+                rec["general_ms_per_step"] = round(general_ms, 3)
+                rec["general_value"] = round(I / (general_ms * 1e-3) / 1e6, 4)
+            if stream and stream.get("general_stream") and stream["general_stream"].get("ms_per_frame") is not None:
+                rec["general_stream_ms_per_frame"] = stream["general_stream"]["ms_per_frame"]      # (no symmetry mode at all, four frames per launch: beside the headline, never `value`)
+            if multi:
+                rec["multi_gpu"] = multi
+            if world == 1 and not args.no_cpu:
+                try:
+                    xlast = xc if F == 1 else xc[F - 1]
+                    xh = torch.view_as_real(xlast).float().cpu().numpy().view(np.complex64).reshape(M, N, T).transpose(2, 1, 0)
+                    plain = not (args.fmod or args.rx_apod or args.window_apod or args.tx_apod or args.gen_apod)
+                    cb, lstep, limg = cpu_baseline(w, xh, apod=w["apod"] if plain else None)
+                    rec["cpu_baseline"] = cb[0]
+                    if len(cb) > 1:
+                        rec["cpu_baseline_tuned"] = cb[1]
+                    # parity of the very frame that was timed (last timed step, the kernel named in config.kernel_name) against the CPU
+                    # port on the baseline's pixel lattice -- outside the timed region
+                    if plain and limg is not None:
+                        from oracle import das_ref
+                        img = torch.view_as_real(yimg.reshape(F, -1)[F - 1]).float().cpu().numpy().view(np.complex64).reshape(w["I1"], w["I2"], order="F")
+                        den = float(np.abs(limg).max())
+                        err32 = float(np.abs(img[::lstep, ::lstep] - limg).max()) / (den if den > 0 else 1.0)
+                        # the judge of parity is the DOUBLE-precision port (the float32 port's own rounding -- fp32 delays at tau*fs ~ 3e3
+                        # samples -- is ~1.5e-4 of the maximum at C3, above the kernel's): every other lattice pixel per axis
+                        s2 = 2 * lstep
+                        ap = () if w["apod"] is None else (w["apod"][::s2, ::s2],)
+                        ref = das_ref.das_spec("DAS", w["Pi"][:, ::s2, ::s2, :], w["Pr"], w["Pv"], w["Nv"], xh, w["t0"], w["fs"],
+                                               1.0 / np.float64(np.float32(1.0 / w["c0"])), VS="plane-waves" not in w["opt"],
+                                               DV="diverging-waves" in w["opt"], interp=w["interp"], apod=ap, prec="double")[:, :, 0, 0, 0]
+                        den64 = float(np.abs(ref).max())
+                        err = float(np.abs(img[::s2, ::s2] - ref).max()) / (den64 if den64 > 0 else 1.0)
+                        tol = 2e-3 if w["prec"] == "halfT" else 1e-4
+                        rec["parity_check"] = {"rel_err": float(f"{err:.3e}"), "tol": tol, "pixels": int(ref.size), "ok": bool(err <= tol and den64 > 0),
+                                               "against": "oracle/das_ref.c in double precision (the C restatement the cpu_baseline times in float32) on "
+                                                          "every %dth pixel per axis of the frame of the last timed step; max |gpu - cpu| / max |cpu|" % s2,
+                                               "rel_err_vs_float32_port": float(f"{err32:.3e}"), "pixels_float32_port": int(limg.size),
+                                               "kernel": plan.kernel_name()}
+                except Exception as ex:  # report, never hide
+                    rec["cpu_baseline"] = {"value": None, "unit": "Mpixel/s", "cores": os.cpu_count(), "kind": "port",
+                                           "sample": f"FAILED: {ex!r}"}
         if args.checksum:
             raw = torch.view_as_real(yimg.reshape(-1)).cpu().numpy().tobytes()
             try:

@@ -285,7 +285,7 @@ def test_bench_two_ranks_over_rccl_matches_one_rank(tmp_path):
     """(>= 2 GPUs) ``bench.py --gpus 2`` as the driver launches it: two ranks over RCCL, pixel slabs + one all_gather; the gathered image
     has the checksum of the one-GPU image and the line carries ``multi_gpu.rccl_ranks == 2``"""
     _need_devices(2)
-    common = ["--workload", "c2", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-traffic", "--checksum"]
+    common = ["--workload", "c2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-traffic", "--checksum"]
     env = {"QDAS_CACHE_DIR": str(tmp_path), "QDAS_KSPLIT": "1"}        # (one summation order whatever the slab size: bit-identical images; both runs in lateral-mirror mode -- N = 2: mirror slabs)
     one = _bench(["--gpus", "1"] + common, env)
     two = _bench(["--gpus", "2"] + common, env)
@@ -295,7 +295,7 @@ def test_bench_two_ranks_over_rccl_matches_one_rank(tmp_path):
 
 def test_bench_shared_gpu_plumbing_prints_one_line(tmp_path):
     """one GPU, two ranks sharing it (gloo): the self-launch, the slab split, the gather and the single JSON line of ``bench.py --gpus 2``"""
-    common = ["--workload", "c1", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-traffic", "--checksum"]
+    common = ["--workload", "c1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-traffic", "--checksum"]
     env = {"QDAS_CACHE_DIR": str(tmp_path), "QDAS_KSPLIT": "1"}
     one = _bench(["--gpus", "1"] + common, env)
     two = _bench(["--gpus", "2"] + common, dict(env, QDAS_BENCH_SHARE_GPU="1"))
@@ -308,7 +308,7 @@ def test_bench_shared_gpu_folded_replication_stream(tmp_path):
     one broadcast of the packed upper triangle, PREFOLDED mirror-slab plans) -- the plumbing of that leg, the bytes that travel, and the image against the
     headline's (the same kernels on the same folded samples)"""
     env = {"QDAS_CACHE_DIR": str(tmp_path), "QDAS_BENCH_SHARE_GPU": "1"}
-    two = _bench(["--gpus", "2", "--workload", "c3", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-traffic", "--no-general"], env)
+    two = _bench(["--gpus", "2", "--workload", "c3", "--steps", "1", "--warmup", "1", "--full", "--no-cpu", "--no-traffic", "--no-general"], env)
     fs = two["multi_gpu"]["stream_folded_replication"]
     assert two["n_gpus"] == 2 and fs and isinstance(fs["ms_per_step"], float), two["multi_gpu"]
     assert fs["bytes_per_frame"] == 256 * 257 // 2 * 2816 * 8 and fs["bytes_per_frame"] * 2 < two["multi_gpu"]["x_bytes"] * 1.01
@@ -320,7 +320,7 @@ def test_bench_shared_gpu_prefolded_timed_region_and_balanced_slabs(tmp_path):
     upper triangle replicated, QDAS_PLAN_PREFOLDED mirror-slab plans), reports the fold + replication time beside it, the column ranges of equal measured cost and who
     was in the process group; the image is the folding run's bit for bit."""
     env = {"QDAS_CACHE_DIR": str(tmp_path), "QDAS_BENCH_SHARE_GPU": "1"}
-    common = ["--gpus", "2", "--workload", "c3", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-traffic", "--no-general", "--checksum"]
+    common = ["--gpus", "2", "--workload", "c3", "--steps", "1", "--warmup", "1", "--full", "--no-cpu", "--no-traffic", "--no-general", "--checksum"]
     plain = _bench(common, env)
     pre = _bench(common + ["--prefolded", "--balance"], env)
     mg = pre["multi_gpu"]

@@ -3,7 +3,7 @@
 # translation unit (-DQDAS_UNITY) with the given QDAS_ABL bit mask (see das_tile_impl.h); extra flags via EXTRA, e.g.
 #   tools/ablate.sh 1 4 8            -> tools/abl/libqdas_abl{1,4,8}.so
 #   EXTRA=-DQDAS_PROF=1 tools/ablate.sh 0 && mv tools/abl/libqdas_abl0.so tools/abl/libqdas_prof.so    (tools/phase_timers.py)
-# then  QDAS_LIB=tools/abl/libqdas_ablN.so python bench.py --no-cpu
+# then  QDAS_LIB=tools/abl/libqdas_ablN.so python bench.py --full --no-cpu
 set -e
 cd "$(dirname "$0")/../qups_amd/csrc"
 mkdir -p ../../tools/abl

@@ -4,7 +4,7 @@
 R=${1:-2}
 run() { # label env...
   local label=$1; shift
-  v=$(env "$@" QDAS_BENCH_CHILD=1 python bench.py --steps 6 --warmup 2 --no-cpu --no-traffic --no-general 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['roofline']['kernel_ms'])" 2>/dev/null)
+  v=$(env "$@" QDAS_BENCH_CHILD=1 python bench.py --steps 6 --warmup 2 --full --no-cpu --no-traffic --no-general 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['roofline']['kernel_ms'])" 2>/dev/null)
   echo "$label|$v"
 }
 for r in $(seq $R); do

@@ -3,7 +3,7 @@
 #   tools/jit_specs_collect.sh > tests/jit_kernels.txt     (on a GPU box: the specs depend on probed tile shapes)
 # tests/test_jit.py rebuilds each of them WITHOUT a device and fails on spilled VGPRs / scratch.
 L=$(mktemp); export QDAS_JIT_SPEC_LOG=$L
-Q="--no-cpu --no-traffic --no-general --steps 2 --warmup 1"
+Q="--full --no-cpu --no-traffic --no-general --steps 2 --warmup 1"
 b() { python bench.py "$@" $Q > /dev/null 2>&1; }
 b; b --workload c2; b --workload c5; b --workload c1
 b --no-fold; b --frames 4; QDAS_NO_MIRROR=1 b; QDAS_NO_MIRROR=1 b --no-fold; QDAS_NO_MIRROR=1 b --workload c2; QDAS_NO_MIRROR=1 b --workload c1

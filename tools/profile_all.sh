@@ -14,7 +14,7 @@ export QDAS_JIT_SPEC_LOG=$OUT/jit_specs.txt      # every hiprtc build of this ru
 cd $REPO
 b() { # name args...
   local name=$1; shift
-  python bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || echo "bench $name FAILED" >> $OUT/errors.txt
+  python bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || echo "bench $name FAILED" >> $OUT/errors.txt
   [ -s $OUT/bench_$name.err ] || rm -f $OUT/bench_$name.err
 }
 # ---- headline (the driver's command) and the other BASELINE configurations, with cpu_baseline + parity_check + live traffic
