@@ -33,13 +33,15 @@ hipError_t lazy_tile_launch(const LazySpec &k, const TileParams &P, unsigned gri
 void lazy_tile_reset();
 const std::string &lazy_tile_last();
 std::string jit_compile_source(const std::string &src, std::vector<char> *code, std::string *key_out, bool use_disk);
-std::string jit_get_kernel_source(const std::string &src, int device, hipFunction_t *fn, std::string *key_out);
 
 std::string jit_source(const JitSpec &k);
 std::string jit_spec_string(const JitSpec &k);      // every field, "raw:name=value,..." (QDAS_JIT_SPEC_LOG; qdas_debug_jit_compile parses it back)
 // "" on success, else the reason (hiprtc missing, compile log, ...)
 std::string jit_compile(const JitSpec &k, std::vector<char> *code, std::string *key_out, bool use_disk = true);
-std::string jit_get_kernel(const JitSpec &k, int device, hipFunction_t *fn, std::string *key_out);
+// The kernel of a plan-specialised build, from the registry (jit.hip): built, vetted and remembered per spec.  `k`: the spec as asked; on return, the
+// spec built (the plain pair loop, ...).  fn == nullptr: not to be launched, err says why.
+struct JitKernel { hipFunction_t fn; std::string key, err; };
+JitKernel jit_kernel(JitSpec &k, int device);
 hipError_t jit_launch(hipFunction_t fn, const TileParams &P, unsigned grid, unsigned block, size_t lds, hipStream_t s);
 
 }  // namespace qdas

@@ -954,7 +954,7 @@ static int plan_stage_shape(qdas_plan *pl, const qdas_desc *desc, PlanBuild &b) 
     const bool jit_on = (desc->plan_flags & QDAS_PLAN_JIT) && !b.sw.no_jit;
     const bool f16 = z.dtype == QDAS_F16;
     // (fp32 frames with a pixel x receiver weight took this shape in round 6 as well: one accumulator per pixel -- TileCfg::ONEACC -- made room for the weighted totals, and a build
-    //  that still needs scratch is rebuilt with the plain pair loop, jit_get_kernel_nospill: C3 with a generated f/1.5 mask 13.3 -> see profiles/r06.
+    //  that still needs scratch is rebuilt with the plain pair loop, jit.hip jit_kernel: C3 with a generated f/1.5 mask 13.3 -> see profiles/r06.
     //  fp16 data: the two-window-set plans only -- one set of 64 transmits measured SLOWER on BASELINE C5 without the mirror mode, 2.37 -> 2.80 ms: M = 96 is 1.5 such blocks)
     if (!(jit_on && (z.dtype == QDAS_F32 || f16) && !t.big && !t.bf && !t.syn && !t.bpix && t.narrow == 0 && !t.stage_shift && !t.cinv_pix
           && !(f16 && (t.sym || !t.mir)) && pl->no_fallback && !getenv("QDAS_NO_STAGE_SHAPE") && !getenv("QDAS_JIT_MB") && !getenv("QDAS_JIT_W"))) return QDAS_OK;
@@ -1018,46 +1018,6 @@ static size_t jit_tile_lds(const JitSpec &k, uint64_t tN, uint64_t tM, uint32_t 
     return hdr + body;
 }
 
-// "No kernel spills" is a property the library enforces, not a sentence: a build that uses scratch memory (the long-stage two-window-set fp32 shapes are at the
-// register limit -- delay kinds, a split aperture, roles swapped move them by a register or two) is rebuilt with the plain instead of the software-pipelined
-// pair loop (16 tap registers less; same-box A/B < 1 %: profiles/r06/oneacc_ab.txt).  QDAS_JIT_SPEC_LOG=<file> logs the final spec of every build:
-// tests/test_jit.py rebuilds those (tests/jit_kernels.txt) without a device and fails on a spilled register.
-static std::string jit_get_kernel_nospill(JitSpec &k, int device, hipFunction_t *fn, std::string *key) {
-    // (roles swapped -- stage elements with their own delay kind and {t0, normal} records -- are known to need the plain loop: asked for up front, so that no spilling build is made at all)
-    if (!k.plain && k.mir && !k.sym && k.dtype == QDAS_F32 && k.mb >= 32 && k.has_st) k.plain = 1;
-    std::string err = jit_get_kernel(k, device, fn, key);
-    auto scratch_of = [](hipFunction_t f) -> int {
-        int scratch = 0;
-        if (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        return scratch;
-    };
-    if (err.empty() && !k.plain && k.mir && !k.sym && k.dtype == QDAS_F32 && k.mb >= 32 && scratch_of(*fn) > 0) {
-        k.plain = 1;
-        hipFunction_t fn2 = nullptr;
-        std::string key2;
-        const std::string err2 = jit_get_kernel(k, device, &fn2, &key2);
-        if (err2.empty()) { *fn = fn2; *key = key2; } else k.plain = 0;
-    }
-    // A build that STILL uses scratch memory is not used at all (round 6).  Not a matter of speed: the pair loops read their taps with inline-asm ds_read
-    // instructions and wait for them by hand (s_waitcnt lgkmcnt further down); a register the compiler spills between the two is stored BEFORE its
-    // data has arrived.  Fuzz seed 126301 with hiprtc builds forced found such a build (roles swapped onto two transmits, 16-element stages of 384-sample
-    // windows, N = 2 as a constant: 352 spilled registers): images that differed from run to run by 0.8 % of the peak in the pixels of one wave.  The plan
-    // keeps the prebuilt / built-on-demand kernel of its shape (checked for spills at build time: tests/test_build_regs.py, tile_variant_check).
-    if (err.empty()) {
-        const int sc = scratch_of(*fn);
-        if (sc > 0 && !getenv("QDAS_JIT_ALLOW_SCRATCH")) {
-            *fn = nullptr;
-            return "hiprtc build uses " + std::to_string(sc) + " bytes of scratch memory per lane (spilled registers): not used";
-        }
-    }
-    if (err.empty()) {
-        if (const char *lf = getenv("QDAS_JIT_SPEC_LOG")) {
-            if (FILE *f = fopen(lf, "a")) { fprintf(f, "%s\n", jit_spec_string(k).c_str()); fclose(f); }
-        }
-    }
-    return err;
-}
-
 // QDAS_PLAN_JIT: the tiled kernel compiled for this plan's sizes (jit.hip).  A failure is not an error: the plan keeps its prebuilt kernel and
 // qdas_last_error() says why -- unless the plan's mode exists as a hiprtc build only: *remake = the plan flag to add for a second attempt without it.
 static int plan_jit(qdas_plan *pl, const qdas_desc *desc, int *remake) {
@@ -1093,11 +1053,10 @@ static int plan_jit(qdas_plan *pl, const qdas_desc *desc, int *remake) {
     if (const char *e = getenv("QDAS_JIT_NBUF")) { const int nb = atoi(e); if (nb >= 2 && nb <= 4) k.nbuf = nb; }
     if (const char *e = getenv("QDAS_JIT_W")) { const int wv = atoi(e); if (wv >= 64 && wv <= 1024 && wv % 64 == 0) k.w = wv; }      // (experiments: tiles that do not fit go to the generic kernel)
     pl->jit_lds = dt == QDAS_F64 ? 0 : jit_tile_lds(k, t.N, t.M, t.act_bytes, t.wtab != nullptr);       // (fp64 data: the prebuilt configuration's own LDS image, das_tile.hip)
-    std::string key;
-    std::string err = pl->jit_lds > (size_t)160 * 1024 ? std::string("LDS image too large for the requested configuration")
-                                                       : jit_get_kernel_nospill(k, pl->device, &pl->jit_fn, &key);
-    if (err.empty()) { pl->jit_tag = "jit " + key; pl->jit_mb = k.mb; pl->jit_w = k.w; return QDAS_OK; }
-    pl->jit_fn = nullptr; g_err = "QDAS_PLAN_JIT: " + err + " -- using the prebuilt kernel";
+    const JitKernel jk = pl->jit_lds > (size_t)160 * 1024 ? JitKernel{nullptr, "", "LDS image too large for the requested configuration"} : jit_kernel(k, pl->device);
+    pl->jit_fn = jk.fn;
+    if (jk.fn) { pl->jit_tag = "jit " + jk.key; pl->jit_mb = k.mb; pl->jit_w = k.w; return QDAS_OK; }
+    g_err = "QDAS_PLAN_JIT: " + jk.err + " -- using the prebuilt kernel";
     const bool unfolded = dt == QDAS_F32 && t.sym && !t.fold;                  // (likewise: the general kernels then)
     if ((dt == QDAS_F32 && t.mir && !t.sym && (t.apix || t.gen_kind)) || unfolded)      // exists only as a hiprtc build: the same plan without the mode
         *remake = unfolded ? QDAS_PLAN_NO_RECIPROCAL : QDAS_PLAN_NO_MIRROR;
@@ -1867,38 +1826,18 @@ static int lut_tiled(const qdas_lut_desc *d, const void *x, void *y, hipStream_t
             if (ks2 > 1 && !part2) ks2 = 1;
             k.ksplit = ks2;
             const size_t lds = jit_tile_lds(k, kN, kM, 0, false);
-            hipFunction_t fn = nullptr;
-            std::string key;
-            const std::string keep_err = g_err;
             if (lds > (size_t)160 * 1024) return 1;
-            // (the resolved kernel of a spec is remembered: jit_get_kernel hashes the source AND every embedded header per call -- 0.1 ms, twice a C1-sized call's kernel)
-            {
-                static std::mutex mu;
-                struct Hit { JitSpec k; int dev; hipFunction_t fn; std::string key; };
-                static std::vector<Hit> hits;
-                bool have = false;
-                { std::lock_guard<std::mutex> lk(mu); for (const Hit &h : hits) if (h.dev == dev && !memcmp(&h.k, &k, sizeof k)) { fn = h.fn; key = h.key; have = true; break; } }
-                if (have && !fn) return 1;               // (remembered: no compiler, or a build that would spill -- the general flavour, without asking again)
-                if (!have) {
-                    const JitSpec asked = k;
-                    const bool failed = !jit_get_kernel_nospill(k, dev, &fn, &key).empty();      // (no compiler: not an error)
-                    if (failed) { fn = nullptr; g_err = keep_err; (void)hipGetLastError(); }
-                    {
-                        std::lock_guard<std::mutex> lk(mu);
-                        hits.push_back(Hit{asked, dev, fn, key});
-                        if (hits.size() > 64) hits.erase(hits.begin());
-                    }
-                    if (failed) return 1;
-                }
-            }
+            const std::string keep_err = g_err;
+            const JitKernel jk = jit_kernel(k, dev);
+            if (!jk.fn) { g_err = keep_err; (void)hipGetLastError(); return 1; }      // (no compiler, or a build that would spill: the general flavour)
             t.probe = 0; t.probe_w = 0; t.mir = 1; t.ksplit = ks2; t.part = (float2 *)part2;
             if (hipMemsetAsync(counter, 0, sizeof(uint32_t), s) != hipSuccess) return 0;
-            if (launch_tile(t, dt, nt2, s, fn, lds) != hipSuccess) return 0;
+            if (launch_tile(t, dt, nt2, s, jk.fn, lds) != hipSuccess) return 0;
             if (verify) {
                 if (hipMemcpyAsync(hc, counter, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return 0;
                 if (hc[0] != 0 || hc[1] != 0) return 1;          // the tables changed under the same pointers: redone below, every pixel rewritten
             }
-            g_lut_last = "tiled,mirror,mb=32,W=128 [jit " + key + "]";
+            g_lut_last = "tiled,mirror,mb=32,W=128 [jit " + jk.key + "]";
             return -1;
         };
         if (ok && memo >= 3 && memo <= 6) {

@@ -240,8 +240,8 @@ def test_roles_swapped_onto_one_or_two_transmits_is_reproducible(seq, M, monkeyp
     """Round 6, fuzz seed 126301 with hiprtc builds forced: 48 receivers, ONE focused (or diverging) transmit, a coarse pixel grid -- the plan swaps the roles
     of the apertures (the transmit becomes the stage side; 16-element stages of 384-sample windows).  The plan-specialised build of that shape SPILLED
     352 registers, and a register spilled between an inline-asm LDS read and the hand-placed wait for it is stored before its data has arrived: images
-    that differed from run to run in one wave of a tile.  A hiprtc build that uses scratch memory is no longer used (``csrc/qdas_api.hip``
-    ``jit_get_kernel_nospill``).  Here: noise frames (smooth targets hide a wrong sample), six runs bit for bit the same, against the oracle."""
+    that differed from run to run in one wave of a tile.  A hiprtc build that uses scratch memory is no longer used (``csrc/jit.hip``
+    ``scratch_refusal``).  Here: noise frames (smooth targets hide a wrong sample), six runs bit for bit the same, against the oracle."""
     import torch
     from oracle import das_oracle as O
     from qups_amd import DasPlan, build_problem, parse_options
