@@ -466,6 +466,41 @@ typedef struct qdas_iir_desc {
 } qdas_iir_desc;
 int qdas_iir(const qdas_iir_desc *desc, const void *x, void *y, void *stream);
 
+/* ---- Aperture-reduction images of a receive-kept image (SYN output of DAS, I1 x I2 x I3 x ... x N): the MATLAB branches of the reference's
+ * kern/slsc.m (average / ensemble estimator, optional time-kernel dimension), kern/dmas.m, kern/cohfac.m and kern/pcf.m (coherence.hip).
+ * x: DEVICE array of `dtype` (QDAS_F64 | QDAS_F32), real or interleaved complex, in a strided layout: the output pixels are up to three
+ * (size, stride) groups, group 0 the fastest; the reduced aperture has N elements at stride strideN, an optional second reduced dimension K at
+ * strideK (SLSC: the time kernel `kdim`; cohfac: its second `dim`; K = 0 reads as 1).  Strides count elements (complex samples when cplx).
+ * Pixels should be the fastest dimension (coalesced loads); any strides are computed correctly.
+ * y: DEVICE array of P = size[0] size[1] size[2] outputs, group 0 fastest: SLSC / DMAS: `dtype`, complex when cplx (SLSC's imaginary part is 0 in
+ * exact arithmetic and is written as such, except NaN where the reference gives NaN); cohfac, pcf: real `dtype` (pcf's w).  y2: pcf's sf (real),
+ * NULL otherwise.  The sizes are taken as given: an unused group is (1, 0), and a size of 0 is an empty image -- the arguments are validated,
+ * nothing is launched, x / y / y2 may be NULL.  Lags (SLSC, DMAS): the range lag_lo .. lag_hi when lags == NULL (a scalar L of the reference is 1 .. L), else the host
+ * table lags[0 .. nlags-1] (the reference's vector L; read during the call only; lags above 2047 that have pairs: QDAS_EUNSUPPORTED).  SLSC
+ * normalises by L = the number of lags as given (duplicates and lags >= N included, kern/slsc.m:136-139) and counts lag 0 once (the MATLAB branch,
+ * not src/slsc.cl); an empty set is QDAS_EINVAL.  DMAS uses the lags in 1 .. N-1 (an empty set gives 0).  gamma: pcf's gamma (the reference's default
+ * is 1; 0 is taken as given).  One kernel launch on `stream`, no temporaries, no host synchronisation. */
+#define QDAS_COH_SLSC_AVERAGE  1
+#define QDAS_COH_SLSC_ENSEMBLE 2
+#define QDAS_COH_DMAS          3
+#define QDAS_COH_COHFAC        4
+#define QDAS_COH_PCF           5
+typedef struct qdas_coherence_desc {
+    int32_t  method;              /* QDAS_COH_*                                  */
+    int32_t  dtype;               /* QDAS_F64 | QDAS_F32                         */
+    int32_t  cplx;                /* samples are interleaved complex             */
+    int32_t  device;              /* HIP device ordinal, -1 = current            */
+    uint64_t N, K;                /* reduced aperture; second reduced dimension  */
+    int64_t  strideN, strideK;
+    uint64_t size[3];             /* pixel groups, fastest first; unused: (1, 0) */
+    int64_t  stride[3];
+    uint64_t lag_lo, lag_hi;      /* lag range when lags == NULL                 */
+    const int64_t *lags;          /* host lag table, or NULL                     */
+    uint64_t nlags;
+    double   gamma;               /* pcf                                         */
+} qdas_coherence_desc;
+int qdas_coherence(const qdas_coherence_desc *desc, const void *x, void *y, void *y2, void *stream);
+
 /* ---- Temporaries of the stream entries (qdas_shift_sum, qdas_das_lut, qdas_greens, qdas_convd's FFT path): taken from an arena the library keeps per (device,
  * stream).  One such call at a time runs per (device, stream) -- a second thread on the same stream waits --, and a call MAY BLOCK the host: when the stream's
  * previous call outgrew the arena (the next call waits for it, then regrows the arena to what that call needed, up to 512 MiB) or asks for a single temporary above

@@ -35,6 +35,14 @@
  *         csizes = [C M N S dtype cplx shape bcast y_real] (include/qdas.h qdas_convd_desc); z is C x L x S
  *   y   = qdas_mex('hilbert', psizes, x, tvars)                           src/ChannelData.m:935-966 (+ downmix :757-766)
  *         psizes = [T K Nfft in_type], tvars = [fs t0 fdown]; x real single or int16 T x K; y is Nfft x K complex single
+ * Aperture-reduction images of a receive-kept image (kern/slsc.m, dmas.m, cohfac.m, pcf.m; the MATLAB branches), x real or complex single / double:
+ *   z       = qdas_mex('slsc', ksz, x, L, method)   method 'average' | 'ensemble'; L: [] (max(1, floor(N/4))), a scalar (lags 1:L) or a vector of lags
+ *   z       = qdas_mex('dmas', ksz, x, L)           L: [] (1:N-1), a scalar (1:L) or a vector (intersect(1:N-1, L))
+ *   r       = qdas_mex('cohfac', ksz, x)            over both reduced dimensions
+ *   [w, sf] = qdas_mex('pcf', ksz, x, gamma)        complex x only; gamma: [] = 1.  (With -DQDAS_MEX_GPU, sf returns as a host array.)
+ *         ksz = [A N B K C kfirst]: x is A x N x B x K x C column-major (as kern/slsc.m's OpenCL branch sizes it: A = prod(sz(1:dim-1)), N = sz(dim),
+ *         ...), N the reduced aperture, K a second reduced dimension (slsc's kdim, cohfac's second dim; omitted = 1), kfirst = 1: x is A x K x B x N x C
+ *         (kdim < dim).  The result is A x B x C (the caller reshapes it to size(x) with the reduced dimensions set to 1); complex for complex slsc / dmas.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
  * pass as device pointers and the result is a gpuArray.
  *
@@ -55,6 +63,7 @@
  */
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include "mex.h"
 #ifdef QDAS_MEX_GPU
@@ -519,14 +528,102 @@ static mxArray *cmd_hilbert(int nrhs, const mxArray *prhs[]) {
     return conclude(rc, host);
 }
 
+/* z = qdas_mex('slsc' | 'dmas' | 'cohfac' | 'pcf', ksz, x, ...) -- kern/slsc.m:187-223, kern/dmas.m:73-79, kern/cohfac.m:64, kern/pcf.m:80-107 */
+static void cmd_coherence(const char *cmd, int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
+    const int slsc = !strcmp(cmd, "slsc"), dmas = !strcmp(cmd, "dmas"), pcf = !strcmp(cmd, "pcf");
+    const int maxin = slsc ? 4 : (dmas || pcf ? 3 : 2);
+    if (nrhs < 2 || nrhs > maxin) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('%s', ksz, x%s)", cmd, slsc ? ", L, method" : dmas ? ", L" : pcf ? ", gamma" : "");
+    qdas_coherence_desc d;
+    memset(&d, 0, sizeof d);
+    d.device = -1;
+    d.gamma = 1.0;
+    d.method = slsc ? QDAS_COH_SLSC_AVERAGE : dmas ? QDAS_COH_DMAS : pcf ? QDAS_COH_PCF : QDAS_COH_COHFAC;
+    const mxArray *k = prhs[0], *xa = prhs[1];
+    const size_t nk = mxGetNumberOfElements(k);
+    const uint64_t A = (uint64_t)num_at(k, 0, "ksz"), N = (uint64_t)num_at(k, 1, "ksz"), B = nk > 2 ? (uint64_t)num_at(k, 2, "ksz") : 1;
+    const uint64_t K = nk > 3 ? (uint64_t)num_at(k, 3, "ksz") : 1, Cc = nk > 4 ? (uint64_t)num_at(k, 4, "ksz") : 1;
+    const int kfirst = nk > 5 && num_at(k, 5, "ksz") != 0;
+    const mxClassID cls = mxGetClassID(xa);
+    if (cls != mxDOUBLE_CLASS && cls != mxSINGLE_CLASS) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "%s: x must be single or double.", cmd);
+    d.dtype = cls == mxDOUBLE_CLASS ? QDAS_F64 : QDAS_F32;
+    d.cplx = mxIsComplex(xa) ? 1 : 0;
+    if (pcf && !d.cplx) mexErrMsgIdAndTxt("QUPS:pcf:realInput", "Input must be complex.");
+    const uint64_t R1 = kfirst ? K : N, R2 = kfirst ? N : K;            /* x is A x R1 x B x R2 x C */
+    d.N = N; d.K = K;
+    d.strideN = (int64_t)(kfirst ? A * R1 * B : A);
+    d.strideK = (int64_t)(kfirst ? A : A * R1 * B);
+    d.size[0] = A; d.stride[0] = 1;
+    d.size[1] = B; d.stride[1] = (int64_t)(A * R1);
+    d.size[2] = Cc; d.stride[2] = (int64_t)(A * R1 * B * R2);
+    const mxArray *Ltab = NULL;                                        /* a lag vector: copied into a table right before the launch */
+    if (slsc || dmas) {
+        const mxArray *L = nrhs > 2 ? prhs[2] : NULL;
+        if (!L || mxIsEmpty(L)) { d.lag_lo = 1; d.lag_hi = slsc ? (N / 4 > 1 ? N / 4 : 1) : N - 1; }
+        else if (mxGetNumberOfElements(L) == 1) {
+            const double l = num_at(L, 0, "L");
+            if (l < 0) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "%s: lags must be non-negative.", cmd);
+            d.lag_lo = 1; d.lag_hi = (uint64_t)l;
+        } else {
+            (void)num_at(L, 0, "L");                                   /* (raises here for a complex or non-numeric L, before anything is staged) */
+            d.nlags = mxGetNumberOfElements(L);
+            Ltab = L;
+        }
+    }
+    if (slsc && nrhs > 3) {
+        char m[16];
+        if (!mxIsChar(prhs[3]) || mxGetString(prhs[3], m, sizeof m) || (strcmp(m, "average") && strcmp(m, "ensemble"))) {
+            mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "slsc: method must be 'average' or 'ensemble'.");
+        }
+        if (!strcmp(m, "ensemble")) d.method = QDAS_COH_SLSC_ENSEMBLE;
+    }
+    if (pcf && nrhs > 2 && !mxIsEmpty(prhs[2])) d.gamma = num_at(prhs[2], 0, "gamma");
+    const size_t es = d.dtype == QDAS_F64 ? 8 : 4, xs = es * (d.cplx ? 2 : 1);
+    const int ycplx = d.cplx && (slsc || dmas);
+    const uint64_t P = A * B * Cc;
+    const mwSize dims[3] = {(mwSize)A, (mwSize)B, (mwSize)Cc};
+    if (P == 0) {                                                      /* an empty image: empty results, nothing staged or launched */
+        plhs[0] = mxCreateNumericArray(3, dims, cls, ycplx ? mxCOMPLEX : mxREAL);
+        if (pcf && nlhs > 1) plhs[1] = mxCreateNumericArray(3, dims, cls, mxREAL);
+        return;
+    }
+    int dev = 0;
+    const void *x = dev_in(xa, (size_t)(A * N * B * K * Cc) * xs, "x", &dev);
+    const size_t bytes = (size_t)P * es * (ycplx ? 2 : 1);
+    mxArray *host;
+    void *y = dev_out(3, dims, cls, ycplx, dev, bytes, &host);
+    int64_t *tab = NULL;
+    if (Ltab) {
+        tab = (int64_t *)malloc(sizeof(int64_t) * d.nlags);
+        if (!tab) { if (host) mxDestroyArray(host); CFAIL("out of host memory."); }
+        for (uint64_t i = 0; i < d.nlags; ++i) tab[i] = (int64_t)num_at(Ltab, (mwSize)i, "L");
+        d.lags = tab;
+    }
+    void *y2 = NULL;
+    mxArray *host2 = NULL;
+    int rc = 0;
+    if (pcf) {
+        host2 = mxCreateNumericArray(3, dims, cls, mxREAL);
+        rc = qdas_device_malloc(&y2, (size_t)P * es, -1);
+    }
+    if (!rc) rc = qdas_coherence(&d, x, y, y2, NULL);
+    free(tab);
+    if (pcf) {
+        if (!rc) rc = qdas_device_copy(mxGetData(host2), y2, (size_t)P * es, 1, -1);
+        if (y2) qdas_device_free(y2, -1);
+        if (rc || nlhs < 2) { mxDestroyArray(host2); host2 = NULL; }   /* (w = qdas_mex('pcf', ...): MATLAB provides one output slot) */
+    }
+    plhs[0] = finish(rc, host, bytes);
+    if (host2) plhs[1] = host2;
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
 #ifdef QDAS_MEX_GPU
     mxInitGPU();
 #endif
-    if (nlhs > 1) mexErrMsgIdAndTxt("QUPS:das_spec:nargout", "qdas_mex returns at most one output.");
+    char cmd[32] = "";
+    if (nrhs >= 1 && mxIsChar(prhs[0]) && mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unreadable command.");
+    if (nlhs > (strcmp(cmd, "pcf") ? 1 : 2)) mexErrMsgIdAndTxt("QUPS:das_spec:nargout", "qdas_mex returns at most one output ('pcf': two).");
     if (nrhs >= 1 && mxIsChar(prhs[0])) {
-        char cmd[32];
-        if (mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unreadable command.");
         if (!strcmp(cmd, "create")) {
             const int slot = create_plan(nrhs - 1, prhs + 1);
             plhs[0] = mxCreateNumericMatrix(1, 1, mxUINT64_CLASS, mxREAL);
@@ -560,6 +657,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "greens")) { plhs[0] = cmd_greens(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "convd")) { plhs[0] = cmd_convd(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "hilbert")) { plhs[0] = cmd_hilbert(nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "slsc") || !strcmp(cmd, "dmas") || !strcmp(cmd, "cohfac") || !strcmp(cmd, "pcf")) { cmd_coherence(cmd, nlhs, plhs, nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();
         } else mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unknown command '%s'.", cmd);

@@ -24,6 +24,7 @@ QDAS_PRE_F32, QDAS_PRE_I16 = 0, 1
 QDAS_CONV_FULL, QDAS_CONV_SAME, QDAS_CONV_VALID, QDAS_CONV_CAUSAL = 0, 1, 2, 3
 QDAS_CONV_X_ONE_COLUMN, QDAS_CONV_X_ONE_SLICE, QDAS_CONV_Y_ONE_COLUMN, QDAS_CONV_Y_ONE_SLICE = 1, 2, 4, 8
 PLAN_NO_RECIPROCAL, PLAN_JIT, PLAN_COPY_INPUTS, PLAN_NO_MIRROR, PLAN_MIRROR_SLAB, PLAN_NO_FOLD, PLAN_APPROX_SYMMETRY, PLAN_PREFOLDED = 1, 2, 4, 8, 16, 32, 64, 128
+COH_SLSC_AVERAGE, COH_SLSC_ENSEMBLE, COH_DMAS, COH_COHFAC, COH_PCF = 1, 2, 3, 4, 5
 RXAPOD_NONE, RXAPOD_ACCEPTANCE, RXAPOD_COSINE, RXAPOD_FNUMBER_PLANAR, RXAPOD_FNUMBER_ORIENTED = 0, 1, 2, 3, 4
 
 # every symbol include/qdas.h declares (tests check the library exports all of them)
@@ -33,6 +34,7 @@ SYMBOLS = (
     "qdas_plan_last_kernel_ms", "qdas_plan_create_sharded", "qdas_plan_execute_sharded", "qdas_plan_sharded_info", "qdas_plan_sharded_mirror",
     "qdas_plan_destroy_sharded", "qdas_DAS", "qdas_DASf", "qdas_DASh", "qdas_delays", "qdas_delaysf",
     "qdas_das_lut", "qdas_das_lut_last_kernel", "qdas_wsinterpd", "qdas_shift_sum", "qdas_greens", "qdas_convd", "qdas_convd_len", "qdas_permute3", "qdas_pre_plan_create", "qdas_pre_execute", "qdas_pre_plan_destroy", "qdas_pre_plan_one_pass", "qdas_last_error", "qdas_version", "qdas_device_malloc", "qdas_device_free", "qdas_device_trim", "qdas_device_copy", "qdas_iir", "qdas_device_info", "qdas_kernel_variant_build", "qdas_kernel_variant_prebuilt",
+    "qdas_coherence",
 )
 
 
@@ -99,6 +101,13 @@ class ConvdDesc(C.Structure):
                 ("shape", C.c_int32), ("bcast", C.c_int32), ("device", C.c_int32), ("y_real", C.c_int32)]
 
 
+class CoherenceDesc(C.Structure):
+    _fields_ = [("method", C.c_int32), ("dtype", C.c_int32), ("cplx", C.c_int32), ("device", C.c_int32),
+                ("N", C.c_uint64), ("K", C.c_uint64), ("strideN", C.c_int64), ("strideK", C.c_int64),
+                ("size", C.c_uint64 * 3), ("stride", C.c_int64 * 3), ("lag_lo", C.c_uint64), ("lag_hi", C.c_uint64),
+                ("lags", C.POINTER(C.c_int64)), ("nlags", C.c_uint64), ("gamma", C.c_double)]
+
+
 class QdasError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libqdas error {code}: {msg}")
@@ -156,6 +165,7 @@ def lib():
     L.qdas_greens.argtypes = [C.POINTER(GreensDesc), C.c_void_p, C.c_void_p]
     L.qdas_convd.argtypes = [C.POINTER(ConvdDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_permute3.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
+    L.qdas_coherence.argtypes = [C.POINTER(CoherenceDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64
     L.qdas_shift_sum.argtypes = [C.POINTER(ShiftDesc), C.c_void_p, C.c_void_p, C.c_void_p]
