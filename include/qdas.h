@@ -142,6 +142,7 @@ extern "C" {
 #define QDAS_EUNSUPPORTED  2 /* valid request the build cannot serve                    */
 #define QDAS_EHIP          3 /* HIP runtime error (message carries hipGetErrorString)   */
 #define QDAS_ENOMEM        4
+#define QDAS_ENOCONV       5 /* an iteration reached its pass cap without a fixed point  */
 
 /* Size/flag constants: the reference's constant-memory symbols QUPS_{T,N,M,I,I1,I2,I3,S},
  * QUPS_{VS,DV}, QUPS_BF_FLAG (reference src/sizes.cu:17-52, src/bf.cu:45-47;
@@ -500,6 +501,37 @@ typedef struct qdas_coherence_desc {
     double   gamma;               /* pcf                                         */
 } qdas_coherence_desc;
 int qdas_coherence(const qdas_coherence_desc *desc, const void *x, void *y, void *y2, void *stream);
+
+/* ---- Travel times through a sound-speed map, and the delay tables sampled from them (eikonal.hip): what the reference's bfEikonal computes with
+ * kern/msfm.m (two arguments: first order, four neighbours) and griddedInterpolant(grd, T, 'cubic', 'none') (src/UltrasoundSystem.m:4283-4321).
+ * c: DEVICE C1 x C2 doubles, C1 fastest (a MATLAB matrix as it lies in memory): the speed; c / dp is msfm's F in cells per second (dp = 1: c is F).
+ * src: HOST 2 x npts doubles, one (first, second) grid coordinate per point in the index base `base` (1: msfm's own), floored to a node as the
+ * reference does; source set k owns the points set_begin[k] .. set_begin[k+1]-1 (a host table of K + 1 entries; NULL: one point per set, npts == K).
+ * A point outside the grid is QDAS_EINVAL.  T: DEVICE C1 x C2 x K doubles, seconds (0 at the source nodes).
+ * qdas_eikonal solves all K sets with the same launches, in double precision, by a block-based fast iterative method that ends at the FIXED POINT of the
+ * update rule (a pass in which no node changes) -- the numbers fast marching produces, to rounding.  It WAITS for the stream (the host ends the iteration).
+ * The number of passes is capped: max_passes, or with 0 qdas_eikonal_pass_cap(C1, C2) = 8 (C1 + C2) + 64.  Reaching the cap returns QDAS_ENOCONV,
+ * the maps are set to NaN.  qdas_eikonal_last_passes: the passes the calling thread's last solve took.  C1 C2 = 0 or K = 0: nothing is launched.
+ * Limits of one call: fewer than 2^24 tiles of 16 x 16 nodes per map, K <= 65535, I <= 2^32 - 256 (QDAS_EUNSUPPORTED beyond).  Work space comes from the stream's arena (below).
+ * qdas_eikonal_tables: tau[i + I k] = map k at pixel i, for I pixels given as DEVICE 2 x I grid coordinates Pi (same base): separable cubic convolution
+ * (Keys, a = -1/2; ghost nodes outside the border by Keys' rule f(-1) = 3 f(0) - 3 f(1) + f(2)), NaN for a pixel outside the grid; a pixel on a node gets the
+ * node's value.  One launch on `stream`, no synchronisation.  tau is the I1 x I2 x I3 x N layout of qdas_das_lut's tables. */
+typedef struct qdas_eikonal_desc {
+    uint64_t C1, C2;              /* grid nodes, C1 fastest                          */
+    uint64_t K;                   /* source sets = maps (at most 65535 per call)     */
+    uint64_t npts;                /* source points in all (qdas_eikonal)             */
+    const uint64_t *set_begin;    /* host, K + 1 entries, or NULL                    */
+    double   dp;                  /* grid step (qdas_eikonal)                        */
+    int32_t  base;                /* index base of src / Pi: 0 | 1                   */
+    int32_t  device;              /* HIP device ordinal, -1 = current                */
+    uint32_t max_passes;          /* 0 = qdas_eikonal_pass_cap(C1, C2)               */
+    uint32_t reserved;
+    uint64_t I;                   /* pixels (qdas_eikonal_tables)                    */
+} qdas_eikonal_desc;
+int qdas_eikonal(const qdas_eikonal_desc *desc, const double *c, const double *src, double *T, void *stream);
+int qdas_eikonal_tables(const qdas_eikonal_desc *desc, const double *T, const double *Pi, double *tau, void *stream);
+int qdas_eikonal_last_passes(void);
+uint32_t qdas_eikonal_pass_cap(uint64_t C1, uint64_t C2);
 
 /* ---- Temporaries of the stream entries (qdas_shift_sum, qdas_das_lut, qdas_greens, qdas_convd's FFT path): taken from an arena the library keeps per (device,
  * stream).  One such call at a time runs per (device, stream) -- a second thread on the same stream waits --, and a call MAY BLOCK the host: when the stream's

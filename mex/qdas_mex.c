@@ -43,6 +43,12 @@
  *         ksz = [A N B K C kfirst]: x is A x N x B x K x C column-major (as kern/slsc.m's OpenCL branch sizes it: A = prod(sz(1:dim-1)), N = sz(dim),
  *         ...), N the reduced aperture, K a second reduced dimension (slsc's kdim, cohfac's second dim; omitted = 1), kfirst = 1: x is A x K x B x N x C
  *         (kdim < dim).  The result is A x B x C (the caller reshapes it to size(x) with the reduced dimensions set to 1); complex for complex slsc / dmas.
+ * Travel times through a speed map (kern/msfm.m with two arguments: first order, four neighbours; what bfEikonal's parfor loops compute one element at a time):
+ *   T       = qdas_mex('msfm', csz, F, src, first, max_passes)
+ *         csz = [C1 C2]; F: C1 x C2 double, host or gpuArray, the speed in cells per second; src: 2 x P double (host), 1-based points, floored to a node;
+ *         first: [] (every point is a source of its own: K = P maps) or the K + 1 offsets (0-based, ascending, last = P) that cut src into K source sets --
+ *         a cell {s1, s2, ...} of 2 x P_k arrays is passed as src = [s1 s2 ...], first = [0 cumsum(P_k)]; max_passes: [] | 0 = the derived cap.
+ *         T is C1 x C2 x K double (seconds).  An empty F or no points: an empty T, nothing is launched.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
  * pass as device pointers and the result is a gpuArray.
  *
@@ -616,6 +622,48 @@ static void cmd_coherence(const char *cmd, int nlhs, mxArray *plhs[], int nrhs, 
     if (host2) plhs[1] = host2;
 }
 
+/* T = qdas_mex('msfm', csz, F, src, first, max_passes) -- kern/msfm.m:93-113 (UseSecond = UseCross = false), one call for every source set */
+static mxArray *cmd_msfm(int nrhs, const mxArray *prhs[]) {
+    if (nrhs < 3 || nrhs > 5) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('msfm', csz, F, src, first, max_passes)");
+    qdas_eikonal_desc d;
+    memset(&d, 0, sizeof d);
+    d.C1 = (uint64_t)num_at(prhs[0], 0, "csz"); d.C2 = (uint64_t)num_at(prhs[0], 1, "csz");
+    d.dp = 1.0; d.base = 1; d.device = -1;
+    const mxArray *sa = prhs[2], *fa = nrhs > 3 ? prhs[3] : NULL;
+    if (!mxIsEmpty(sa) && (mxGetClassID(sa) != mxDOUBLE_CLASS || mxIsComplex(sa) || mxGetNumberOfElements(sa) % 2))
+        mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "msfm: SourcePoints must be a real double 2 x P array.");
+    d.npts = (uint64_t)(mxGetNumberOfElements(sa) / 2);
+    const int sets = fa && !mxIsEmpty(fa);
+    d.K = sets ? (uint64_t)mxGetNumberOfElements(fa) - 1 : d.npts;
+    if (nrhs > 4 && !mxIsEmpty(prhs[4])) d.max_passes = (uint32_t)num_at(prhs[4], 0, "max_passes");
+    const mwSize dims[3] = {(mwSize)d.C1, (mwSize)d.C2, (mwSize)d.K};
+    if (d.C1 * d.C2 == 0 || d.K == 0 || d.npts == 0)                   /* empty in, empty out */
+        return mxCreateNumericArray(3, (const mwSize[3]){(mwSize)d.C1, (mwSize)d.C2, (mwSize)(d.C1 * d.C2 != 0 ? 0 : d.K)}, mxDOUBLE_CLASS, mxREAL);
+    if (mxGetClassID(prhs[1]) != mxDOUBLE_CLASS || mxIsComplex(prhs[1])) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "msfm: the speed map must be real double.");
+    /* the reference's range errors, its texts (kern/msfm.m:96-99) */
+    const double *sp = (const double *)mxGetData(sa);
+    for (uint64_t p = 0; p < 2 * d.npts; ++p) if (!(sp[p] >= 1.0)) mexErrMsgIdAndTxt("QUPS:msfm:sourceRange", "Source points must be >= 1 to be within the field.");
+    for (int dim = 0; dim < 2; ++dim)
+        for (uint64_t p = 0; p < d.npts; ++p)
+            if (sp[2 * p + dim] > (double)(dim ? d.C2 : d.C1))
+                mexErrMsgIdAndTxt("QUPS:msfm:sourceRange", "Source points must be <= %llu in dimension %d to be in the field.", (unsigned long long)(dim ? d.C2 : d.C1), dim + 1);
+    uint64_t *first = NULL;
+    if (sets) {
+        first = (uint64_t *)malloc(sizeof(uint64_t) * (d.K + 1));
+        if (!first) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "out of host memory.");
+        for (uint64_t k = 0; k <= d.K; ++k) first[k] = (uint64_t)num_at(fa, (mwSize)k, "first");
+        d.set_begin = first;
+    }
+    int dev = 0;
+    const size_t bytes = (size_t)(d.C1 * d.C2 * d.K) * 8;
+    const void *c = dev_in(prhs[1], (size_t)(d.C1 * d.C2) * 8, "F", &dev);
+    mxArray *host;
+    void *T = dev_out(3, dims, mxDOUBLE_CLASS, 0, dev, bytes, &host);
+    const int rc = qdas_eikonal(&d, (const double *)c, sp, (double *)T, NULL);
+    free(first);
+    return finish(rc, host, bytes);
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
 #ifdef QDAS_MEX_GPU
     mxInitGPU();
@@ -658,6 +706,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "convd")) { plhs[0] = cmd_convd(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "hilbert")) { plhs[0] = cmd_hilbert(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "slsc") || !strcmp(cmd, "dmas") || !strcmp(cmd, "cohfac") || !strcmp(cmd, "pcf")) { cmd_coherence(cmd, nlhs, plhs, nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "msfm")) { plhs[0] = cmd_msfm(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();
         } else mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unknown command '%s'.", cmd);

@@ -13,7 +13,8 @@ from . import apodization  # noqa: F401,E402
 from . import preproc  # noqa: F401,E402
 from .convd import convd, sosfilt  # noqa: F401,E402
 from .coherence import cohfac, dmas, pcf, slsc  # noqa: F401,E402
+from .eikonal import msfm  # noqa: F401,E402
 from .ultrasound import ChannelData, Scan, Sequence, Transducer, UltrasoundSystem  # noqa: F401,E402
 
 __all__ = ["das_spec", "DasPlan", "MultiDevicePlan", "DasProblem", "DasError", "build_problem", "parse_options", "das_lut", "sample2sep",
-           "wsinterpd2", "convd", "slsc", "dmas", "cohfac", "pcf", "UltrasoundSystem", "Transducer", "Sequence", "Scan", "ChannelData"]
+           "wsinterpd2", "convd", "slsc", "dmas", "cohfac", "pcf", "msfm", "UltrasoundSystem", "Transducer", "Sequence", "Scan", "ChannelData"]

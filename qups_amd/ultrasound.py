@@ -487,6 +487,55 @@ class UltrasoundSystem:
         tau_rx, tau_tx = self.delay_tables(c0, device=dev)
         return self.bfDASLUT(chd, tau_rx, tau_tx, *apods, apod=apod, fmod=fmod, interp=interp, keep_tx=keep_tx, keep_rx=keep_rx, prec=prec, bsize=bsize)
 
+    def bfEikonal(self, chd, c, cgrd=None, *apods, fmod=0.0, interp="cubic", apod=1, keep_rx=False, keep_tx=False, bsize=None,
+                  delay_only=False, prec=None, return_delays=False):
+        """``[b, tau_rx, tau_tx] = bfEikonal(us, chd, med, cgrd, ...)`` (reference ``src/UltrasoundSystem.m:4204-4331``): delay-and-sum with
+        travel times through the sound-speed map ``c``, an array of ``cgrd.size`` (a scalar: homogeneous; there is no ``Medium`` class here).
+        ``cgrd`` defaults to ``us.scan`` and must be a Cartesian scan with one singleton dimension and equal steps in the other two.
+
+        One travel-time map per element is solved on the device (``qups_amd.eikonal``; the reference: one ``msfm`` call per element, ``:4295-4308``)
+        from the element's position floored to a grid node, sampled at the pixels of ``us.scan`` by cubic convolution (NaN outside ``cgrd``; such
+        pixels add nothing to the image), and handed to :meth:`bfDASLUT` without leaving the device.  The transmit tables are the receive tables
+        when ``us.tx is us.rx`` or the positions are equal (``:4300``).  Returns ``b``.  The reference's ``[b, tau_rx, tau_tx] = ...`` is asked for with
+        ``return_delays=True`` (Python has no ``nargout``); ``delay_only=True`` implies it and skips the image (``b`` is then empty, ``:4324``):
+        ``(b, tau_rx, tau_tx)`` with ``tau_rx`` ``I1 x I2 x I3 x N`` and ``tau_tx`` ``I1 x I2 x I3 x 1 x M``."""
+        import torch
+        from . import eikonal as E
+        cgrd = self.scan if cgrd is None else cgrd
+        chds = []
+        if not delay_only:
+            chds, _ = self._chd_array(chd)
+            if not all(int(x.data.shape[x.order.index("M")]) == self.tx.numel for x in chds):       # (:4244-4245)
+                raise DasError("Number of transmits must match number of transmitter elements.")
+            if not all(int(x.data.shape[x.order.index("N")]) == self.rx.numel for x in chds):
+                raise DasError("Number of receives must match number of receiver elements.")
+        og, dp, dims, axes, csz = E.scan_grid(cgrd)
+        if np.ndim(c) == 0:
+            cmap = np.full(csz, float(c))
+        else:
+            if not hasattr(c, "shape"):
+                c = np.asarray(c, dtype=np.float64)
+            if tuple(int(v) for v in c.shape) != tuple(cgrd.size):
+                raise DasError(f"bfEikonal: the sound speed must be a scalar or an array of the grid's size {tuple(cgrd.size)}")
+            cmap = c.reshape(csz)
+        Prc = E.grid_coordinates(self.rx.positions(), og, dp, axes)                                 # (:4283-4284)
+        reuse = E.same_aperture(self)
+        Pvc = Prc if reuse else E.grid_coordinates(self.tx.positions(), og, dp, axes)
+        Isz = self.scan.size
+        Pi = np.asarray(self.scan.positions(), float).reshape(3, -1, order="F")                     # pixels in memory order: I1 fastest
+        Pic = E.grid_coordinates(Pi, og, dp, axes)
+        first = chds[0] if chds else None
+        dev = first.data.device if first is not None and hasattr(first.data, "is_cuda") and first.data.is_cuda else None
+        if dev is None and hasattr(c, "is_cuda") and c.is_cuda:
+            dev = c.device
+        tau_rx = E.travel_time_tables(cmap, dp, Prc, Pic, Isz, device=dev)
+        tau_tx = tau_rx if reuse else E.travel_time_tables(cmap, dp, Pvc, Pic, Isz, device=dev)
+        if delay_only:
+            b = torch.zeros(tuple(Isz) + (self.rx.numel if keep_rx else 1, self.tx.numel if keep_tx else 1, 0), device=tau_rx.device)   # (:4324)
+            return b, tau_rx, tau_tx.unsqueeze(3)
+        b = self.bfDASLUT(chd, tau_rx, tau_tx, *apods, apod=apod, fmod=fmod, interp=interp, keep_tx=keep_tx, keep_rx=keep_rx, prec=prec, bsize=bsize)
+        return (b, tau_rx, tau_tx.unsqueeze(3)) if return_delays else b
+
     def bfDASLUT(self, chd: ChannelData, tau_rx, tau_tx, *apods, apod=1, fmod=0.0, interp="cubic", keep_tx=False,
                  keep_rx=False, prec=None, bsize=None):
         """``b = bfDASLUT(us, chd, tau_rx, tau_tx, ...)`` (reference ``src/UltrasoundSystem.m:4476-4673``):
