@@ -533,6 +533,39 @@ int qdas_eikonal_tables(const qdas_eikonal_desc *desc, const double *T, const do
 int qdas_eikonal_last_passes(void);
 uint32_t qdas_eikonal_pass_cap(uint64_t C1, uint64_t C2);
 
+/* ---- Frequency-domain adjoint beamformer (adjoint.hip): the frequency loop of the reference's bfAdjoint (src/UltrasoundSystem.m:3997-4037) as ONE call.
+ * For every pixel i and selected frequency f_k, with tau_rx(i,n) = |Pr_n - Pi| cinv(i), tau_tx(i,m) = |Pt_m - Pi| cinv(i):
+ *   S[m,v,k] = apod_tx[m,v] exp(-2 pi i f_k del_tx[m,v])
+ *   A[i,v,k] = sum_m exp(-2 pi i f_k tau_tx(i,m)) S[m,v,k],   Ahat = A / ||A[i,:,k]||_2 (norm over v; a zero norm divides, as the reference does)
+ *   R[i,v,k] = sum_n a_n(i,n) exp(+2 pi i f_k tau_rx(i,n)) X[k,v,n]
+ *   b[i]     = sum_k sum_v a_m(i,v) R[i,v,k] conj(Ahat[i,v,k])               keep_tx: no sum over v, b[i,v]
+ *   keep_rx: b[i,n] = sum_k sum_v a_m a_n exp(+2 pi i f_k tau_rx) X[k,v,n] conj(Ahat[i,v,k])           with keep_tx: b[i,n,v]
+ * X: DEVICE complex64 Ksel x V x N, n fastest (MATLAB's N x V x F block as it lies in memory); b: DEVICE complex64 I x [N] x [V], pixel fastest.
+ * Without keep_rx the two contractions run on the f32 matrix cores (v_mfma_f32_32x32x2_f32; the phasor operand is generated per lane, phases formed in
+ * fp64 and reduced to a fractional cycle first); with keep_rx plain vector kernels.  No floating-point atomics: results are bit-reproducible.
+ * Every pointer but `freq` is a DEVICE pointer; freq is a HOST table.  dtype: QDAS_F32 only (QDAS_F16 / QDAS_F64: QDAS_EUNSUPPORTED).
+ * An image without elements (I = 0, N = 0 with keep_rx, V = 0 with keep_tx): nothing is launched.  Otherwise N, V or Ksel = 0 is an empty sum: b is set
+ * to zero by a memset, no kernel runs.  M = 0 with everything else positive is QDAS_EINVAL (the transmit field has no norm).
+ * Work space: the steering matrix S (Ksel V M complex64), the partial images of split frequencies, and -- keep_tx / keep_rx -- per-pixel tables, for
+ * which the pixels are processed in blocks of at most 256 MiB.  It is taken through the stream's arena (below), so the call MAY BLOCK the host: any
+ * single piece above 64 MiB (S at Ksel V M > 2^23, e.g. 1024 x 128 x 128; a full pixel block) is a hipMalloc of its own that is freed, after a
+ * stream synchronisation, before the call returns.  Smaller calls only enqueue work. */
+typedef struct qdas_adjoint_desc {
+    uint64_t I, N, M, V, Ksel;    /* pixels, receivers, transmit elements, transmits, selected frequencies */
+    const float *Pi, *Pr, *Pt;    /* 3 x I, 3 x N, 3 x M positions                    */
+    const float *cinv;            /* 1 / sound speed: cinv_count values               */
+    uint64_t cinv_count;          /* 1 | I                                            */
+    const double *freq;           /* HOST: Ksel frequencies [Hz]                      */
+    const double *del_tx;         /* M x V, m fastest: delays(seq, tx) + t0Offset [s] */
+    const float *apod_tx;         /* M x V, m fastest                                 */
+    const float *a_n;             /* I x N, pixel fastest, or NULL = 1                */
+    const float *a_m;             /* I x V, pixel fastest, or NULL = 1                */
+    int32_t  keep_rx, keep_tx;    /* 0 | 1                                            */
+    int32_t  dtype;               /* QDAS_F32                                         */
+    int32_t  device;              /* HIP device ordinal, -1 = current                 */
+} qdas_adjoint_desc;
+int qdas_adjoint(const qdas_adjoint_desc *desc, const void *X, void *b, void *stream);
+
 /* ---- Temporaries of the stream entries (qdas_shift_sum, qdas_das_lut, qdas_greens, qdas_convd's FFT path): taken from an arena the library keeps per (device,
  * stream).  One such call at a time runs per (device, stream) -- a second thread on the same stream waits --, and a call MAY BLOCK the host: when the stream's
  * previous call outgrew the arena (the next call waits for it, then regrows the arena to what that call needed, up to 512 MiB) or asks for a single temporary above

@@ -49,6 +49,9 @@
  *         first: [] (every point is a source of its own: K = P maps) or the K + 1 offsets (0-based, ascending, last = P) that cut src into K source sets --
  *         a cell {s1, s2, ...} of 2 x P_k arrays is passed as src = [s1 s2 ...], first = [0 cumsum(P_k)]; max_passes: [] | 0 = the derived cap.
  *         T is C1 x C2 x K double (seconds).  An empty F or no points: an empty T, nothing is launched.
+ * The frequency loop of bfAdjoint (src/UltrasoundSystem.m:3997-4037) as one call:
+ *   b       = qdas_mex('adjoint', sizes, xk, f, Pi, Pr, Pt, cinv, del_tx, apod_tx, a_n, a_m, flags)
+ *         sizes = [I N M V F], flags = [keep_rx keep_tx]; the arrays are described at cmd_adjoint below.  b is I x [N] x [V] single complex.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
  * pass as device pointers and the result is a gpuArray.
  *
@@ -263,7 +266,7 @@ static plan_slot *slot_of(const mxArray *h) {
 
 /* ---- the stateless commands: device-pointer entries of the C ABI behind host arrays (staged here) or gpuArrays (passed through) */
 typedef struct { const void *ptr; void *owned; argptr a; } devarg;
-#define QDAS_MEX_MAX_DEVARGS 8
+#define QDAS_MEX_MAX_DEVARGS 12
 static devarg g_da[QDAS_MEX_MAX_DEVARGS];
 static int g_nda = 0;
 static void *g_out_dev = NULL;                          /* device image of a host output */
@@ -664,6 +667,46 @@ static mxArray *cmd_msfm(int nrhs, const mxArray *prhs[]) {
     return finish(rc, host, bytes);
 }
 
+/* b = qdas_mex('adjoint', sizes, xk, f, Pi, Pr, Pt, cinv, del_tx, apod_tx, a_n, a_m, flags) -- the parfor of bfAdjoint (src/UltrasoundSystem.m:3997-4037).
+ * xk: N x V x F single complex (the selected bins of the spectrum, a_mn applied), f: F doubles [Hz] (host), Pi / Pr / Pt: 3 x I / N / M single,
+ * cinv: 1 or I single, del_tx: M x V double (t0Offset added), apod_tx: M x V single, a_n: I x N single or [], a_m: I x V single or [].
+ * b: I x [N] x [V] single complex. */
+static mxArray *cmd_adjoint(int nrhs, const mxArray *prhs[]) {
+    if (nrhs != 12) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('adjoint', sizes, xk, f, Pi, Pr, Pt, cinv, del_tx, apod_tx, a_n, a_m, flags)");
+    qdas_adjoint_desc d;
+    memset(&d, 0, sizeof d);
+    d.I = (uint64_t)num_at(prhs[0], 0, "sizes"); d.N = (uint64_t)num_at(prhs[0], 1, "sizes"); d.M = (uint64_t)num_at(prhs[0], 2, "sizes");
+    d.V = (uint64_t)num_at(prhs[0], 3, "sizes"); d.Ksel = (uint64_t)num_at(prhs[0], 4, "sizes");
+    d.keep_rx = num_at(prhs[11], 0, "flags") != 0; d.keep_tx = num_at(prhs[11], 1, "flags") != 0;
+    d.dtype = QDAS_F32; d.device = -1;
+    const mxArray *xa = prhs[1], *fa = prhs[2];
+    if (!mxIsEmpty(xa) && (mxGetClassID(xa) != mxSINGLE_CLASS || !mxIsComplex(xa)))
+        mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "adjoint: the spectrum must be single complex (half precision is insufficient for frequency-domain beamforming; there is no double path).");
+    if (mxGetNumberOfElements(fa) != d.Ksel || (d.Ksel && (mxGetClassID(fa) != mxDOUBLE_CLASS || mxIsComplex(fa))))
+        mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "adjoint: f must hold one real double per frequency.");
+    for (int k = 3; k <= 6; ++k) if (!mxIsEmpty(prhs[k]) && mxGetClassID(prhs[k]) != mxSINGLE_CLASS) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "adjoint: Pi, Pr, Pt and cinv must be single.");
+    if (!mxIsEmpty(prhs[7]) && mxGetClassID(prhs[7]) != mxDOUBLE_CLASS) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "adjoint: del_tx must be double.");
+    for (int k = 8; k <= 10; ++k) if (!mxIsEmpty(prhs[k]) && mxGetClassID(prhs[k]) != mxSINGLE_CLASS) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "adjoint: apod_tx, a_n and a_m must be single.");
+    d.cinv_count = (uint64_t)mxGetNumberOfElements(prhs[6]);
+    d.freq = (const double *)mxGetData(fa);
+    const mwSize dims[3] = {(mwSize)d.I, (mwSize)(d.keep_rx ? d.N : 1), (mwSize)(d.keep_tx ? d.V : 1)};
+    const size_t bytes = (size_t)dims[0] * dims[1] * dims[2] * 8;
+    if (!bytes) return mxCreateNumericArray(3, dims, mxSINGLE_CLASS, mxCOMPLEX);                    /* empty in, empty out */
+    int dev = 0;
+    const void *x = dev_in(xa, (size_t)(d.N * d.V * d.Ksel) * 8, "xk", &dev);
+    d.Pi = (const float *)dev_in(prhs[3], 3 * (size_t)d.I * 4, "Pi", &dev);
+    d.Pr = (const float *)dev_in(prhs[4], 3 * (size_t)d.N * 4, "Pr", &dev);
+    d.Pt = (const float *)dev_in(prhs[5], 3 * (size_t)d.M * 4, "Pt", &dev);
+    d.cinv = (const float *)dev_in(prhs[6], (size_t)d.cinv_count * 4, "cinv", &dev);
+    d.del_tx = (const double *)dev_in(prhs[7], (size_t)(d.M * d.V) * 8, "del_tx", &dev);
+    d.apod_tx = (const float *)dev_in(prhs[8], (size_t)(d.M * d.V) * 4, "apod_tx", &dev);
+    d.a_n = mxIsEmpty(prhs[9]) ? NULL : (const float *)dev_in(prhs[9], (size_t)(d.I * d.N) * 4, "a_n", &dev);
+    d.a_m = mxIsEmpty(prhs[10]) ? NULL : (const float *)dev_in(prhs[10], (size_t)(d.I * d.V) * 4, "a_m", &dev);
+    mxArray *host;
+    void *b = dev_out(3, dims, mxSINGLE_CLASS, 1, dev, bytes, &host);
+    return finish(qdas_adjoint(&d, x, b, NULL), host, bytes);
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
 #ifdef QDAS_MEX_GPU
     mxInitGPU();
@@ -707,6 +750,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "hilbert")) { plhs[0] = cmd_hilbert(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "slsc") || !strcmp(cmd, "dmas") || !strcmp(cmd, "cohfac") || !strcmp(cmd, "pcf")) { cmd_coherence(cmd, nlhs, plhs, nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "msfm")) { plhs[0] = cmd_msfm(nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "adjoint")) { plhs[0] = cmd_adjoint(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();
         } else mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unknown command '%s'.", cmd);

@@ -35,7 +35,7 @@ SYMBOLS = (
     "qdas_plan_last_kernel_ms", "qdas_plan_create_sharded", "qdas_plan_execute_sharded", "qdas_plan_sharded_info", "qdas_plan_sharded_mirror",
     "qdas_plan_destroy_sharded", "qdas_DAS", "qdas_DASf", "qdas_DASh", "qdas_delays", "qdas_delaysf",
     "qdas_das_lut", "qdas_das_lut_last_kernel", "qdas_wsinterpd", "qdas_shift_sum", "qdas_greens", "qdas_convd", "qdas_convd_len", "qdas_permute3", "qdas_pre_plan_create", "qdas_pre_execute", "qdas_pre_plan_destroy", "qdas_pre_plan_one_pass", "qdas_last_error", "qdas_version", "qdas_device_malloc", "qdas_device_free", "qdas_device_trim", "qdas_device_copy", "qdas_iir", "qdas_device_info", "qdas_kernel_variant_build", "qdas_kernel_variant_prebuilt",
-    "qdas_coherence", "qdas_eikonal", "qdas_eikonal_tables", "qdas_eikonal_last_passes", "qdas_eikonal_pass_cap",
+    "qdas_coherence", "qdas_eikonal", "qdas_eikonal_tables", "qdas_eikonal_last_passes", "qdas_eikonal_pass_cap", "qdas_adjoint",
 )
 
 
@@ -115,6 +115,13 @@ class EikonalDesc(C.Structure):
                 ("I", C.c_uint64)]
 
 
+class AdjointDesc(C.Structure):
+    _fields_ = [("I", C.c_uint64), ("N", C.c_uint64), ("M", C.c_uint64), ("V", C.c_uint64), ("Ksel", C.c_uint64),
+                ("Pi", C.c_void_p), ("Pr", C.c_void_p), ("Pt", C.c_void_p), ("cinv", C.c_void_p), ("cinv_count", C.c_uint64),
+                ("freq", C.c_void_p), ("del_tx", C.c_void_p), ("apod_tx", C.c_void_p), ("a_n", C.c_void_p), ("a_m", C.c_void_p),
+                ("keep_rx", C.c_int32), ("keep_tx", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32)]
+
+
 class QdasError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libqdas error {code}: {msg}")
@@ -178,6 +185,7 @@ def lib():
     L.qdas_eikonal_last_passes.argtypes = []
     L.qdas_eikonal_pass_cap.argtypes = [C.c_uint64, C.c_uint64]
     L.qdas_eikonal_pass_cap.restype = C.c_uint32
+    L.qdas_adjoint.argtypes = [C.POINTER(AdjointDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64
     L.qdas_shift_sum.argtypes = [C.POINTER(ShiftDesc), C.c_void_p, C.c_void_p, C.c_void_p]

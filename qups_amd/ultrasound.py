@@ -72,6 +72,18 @@ class Sequence:
             return tau * np.where(np.all(f[2][None, :] > p[2][:, None], axis=0), 1.0, -1.0)[None, :]
         raise DasError(f"Unknown sequence type {self.type!r}.")
 
+    def t0Offset(self):
+        """``t0 = t0Offset(seq)``: the time offset from the foci to the transducer origin, one value per transmit (reference ``src/Sequence.m:1042-1050``):
+        ``-|focus| / c0`` for FC and VS, ``+|focus| / c0`` for DV, 0 for FSA and PW"""
+        if self.type in ("FSA", "PW"):
+            return np.zeros(1)
+        r = np.sqrt((np.asarray(self.focus, float) ** 2).sum(0)) / self.c0
+        if self.type in ("FC", "VS"):
+            return -r
+        if self.type == "DV":
+            return r
+        raise DasError(f"Unknown sequence type {self.type!r}.")
+
     def apodization(self, tx: "Transducer"):
         """``N x S`` transmit apodization (reference ``src/Sequence.m:953-975``): identity for FSA, ones otherwise"""
         N = tx.numel
@@ -535,6 +547,92 @@ class UltrasoundSystem:
             return b, tau_rx, tau_tx.unsqueeze(3)
         b = self.bfDASLUT(chd, tau_rx, tau_tx, *apods, apod=apod, fmod=fmod, interp=interp, keep_tx=keep_tx, keep_rx=keep_rx, prec=prec, bsize=bsize)
         return (b, tau_rx, tau_tx.unsqueeze(3)) if return_delays else b
+
+    def bfAdjoint(self, chd: ChannelData, *apods, c0=None, fmod=0.0, fthresh=-np.inf, apod=1, Nfft=None, keep_tx=False, keep_rx=False,
+                  bsize=None, verbose=False, return_delays=False, return_bins=False):
+        """``b = bfAdjoint(us, chd, A1, ..., 'c0', c0, 'fmod', fc, 'fthresh', thresh, 'Nfft', K, 'keep_tx', tf, 'keep_rx', tf)`` (reference
+        ``src/UltrasoundSystem.m:3770-4050``): the inner product of the normalised transmitted wave with the received data, in the frequency domain.
+        Output ``I1 x I2 x I3 x F... x [N] x [V]``.
+
+        The spectrum, the frequency selection (``fthresh``: bins where no trace is within ``fthresh`` dB of its own maximum are dropped; bins at or
+        above ``fs / 2`` always) and the routing of the apodization arrays run in torch on the data's device; the reference's loop over frequency
+        blocks is one ``qdas_adjoint`` call per frame (``qups_amd.adjoint``, f32 matrix cores).  ``c0``: a scalar or ``I1 x I2 x I3``.
+
+        ``Nfft``: the frequencies are ``f_k = k fs / Nfft`` throughout.  (The reference builds its phase ramps on the data's own frequency axis, of
+        length ``T``, and takes the step from ``Nfft``: it only runs for ``Nfft == T``.)  ``Nfft >= T`` zero-pads; ``Nfft < T`` raises.
+        Only complex64 data is supported (the reference itself warns that half precision is insufficient; there is no fp64 path).
+        ``bsize`` and ``verbose`` are accepted for signature compatibility: no phasor block is ever stored, so there is nothing to bound.
+        ``return_delays=True`` returns ``(b, tau_rx, tau_tx, tau_foc)`` as the reference's extra outputs: ``tau_rx`` ``I1 x I2 x I3 x N``, ``tau_tx``
+        ``I1 x I2 x I3 x 1 x M`` (element to pixel), ``tau_foc = delays(seq, tx) + t0Offset`` (``M x V``).
+        ``return_bins=True`` appends the ascending 0-based list of the frequency bins that were evaluated to whatever is returned."""
+        import torch
+        from . import adjoint as A
+        if not isinstance(chd, ChannelData):
+            raise DasError("bfAdjoint: chd must be one ChannelData")
+        chd = chd.rectifyDims()
+        x = chd._torch_data()
+        if x.dtype != torch.complex64:
+            raise DasError(f"bfAdjoint: complex64 data only, got {str(x.dtype).replace('torch.', '')} (half precision is insufficient for "
+                           "frequency-domain beamforming; there is no double precision path; real data: hilbert first)")
+        if x.ndim < 3:
+            x = x.reshape(tuple(x.shape) + (1,) * (3 - x.ndim))
+        T, N, V = (int(v) for v in x.shape[:3])
+        M = self.tx.numel
+        if Nfft is not None and int(Nfft) < T:
+            raise DasError(f"bfAdjoint: Nfft ({int(Nfft)}) must be at least the number of samples ({T})")
+        if N != self.rx.numel:
+            raise DasError("Number of receives must match number of receiver elements.")
+        del_tx = np.asarray(self.seq.delays(self.tx), float)
+        if del_tx.shape != (M, V):
+            raise DasError(f"Number of transmits ({V}) must match the sequence's delays ({del_tx.shape[0]} x {del_tx.shape[1]}).")
+        apod_tx = np.broadcast_to(np.asarray(self.seq.apodization(self.tx), float), (M, V))
+        t0off = np.broadcast_to(np.asarray(self.seq.t0Offset(), float).reshape(-1), (V,))
+        t0 = np.asarray(chd.t0, float).reshape(-1)
+        if t0.size not in (1, V):
+            raise DasError("bfAdjoint: t0 must be a scalar or one value per transmit")
+        tau_foc = del_tx + t0off[None, :]
+        Isz = tuple(self.scan.size)
+        I = int(np.prod(Isz))
+        c0 = self.seq.c0 if c0 is None else c0
+        cv = np.asarray(c0.cpu() if hasattr(c0, "cpu") else c0, float)
+        if cv.size != 1 and tuple(cv.shape) + (1,) * (3 - cv.ndim) != Isz:
+            raise DasError(f"bfAdjoint: c0 must be a scalar or an array of the scan's size {Isz}")
+        cinv = 1.0 / cv.reshape(-1, order="F")
+        a_n, a_m, a_mn = A.classify_apods(([] if (np.isscalar(apod) and apod == 1) else [apod]) + list(apods), Isz, N, V)
+        if not x.is_cuda:
+            if not torch.cuda.is_available():
+                raise RuntimeError("qups_amd: no HIP device visible -- the adjoint beamformer has no CPU fallback")
+            x = x.cuda()
+        dev = x.device
+        Fsz = tuple(int(v) for v in x.shape[3:])
+        xf = x.reshape(T, N, V, -1)
+        amn = None if a_mn is None else torch.from_numpy(np.array(a_mn)).to(dev, torch.float32).reshape(1, N, V)
+        # one spectrum per frame (K x N x V each): a frame's numbers do not depend on its neighbours
+        Xf = [A.spectrum(xf[..., f].contiguous(), t0, chd.fs, fmod, Nfft, t0off) for f in range(xf.shape[3])]
+        K = T if Nfft is None else int(Nfft)
+        ksel = A.select_bins(torch.stack(Xf, 3), chd.fs, fthresh) if Xf else np.zeros(0, np.int64)   # (one list for all frames, on the un-apodized spectrum, :3935-3938)
+        if amn is not None:
+            Xf = [X * amn for X in Xf]                         # a_mn is applied to the data (:4022)
+        freq = ksel.astype(np.float64) * (chd.fs / K)
+        kidx = torch.from_numpy(ksel).to(dev)
+        Pi = np.asarray(self.scan.positions(), float).reshape((3, I), order="F")                   # pixels in memory order: I1 fastest
+        Pr, Pt = np.asarray(self.rx.positions(), float), np.asarray(self.tx.positions(), float)
+        flat = lambda a, n: None if a is None else np.asarray(a, float).reshape((I, n), order="F")
+        an, am = flat(a_n, N), flat(a_m, V)
+        Nn, Vv = (N if keep_rx else 1), (V if keep_tx else 1)
+        frames = []
+        for X in Xf:                                                           # one call per frame; the pixel index is column-major (I1 fastest)
+            bf = A.adjoint(X[kidx].permute(0, 2, 1), freq, Pi, Pr, Pt, cinv, tau_foc, apod_tx, an, am, keep_rx=keep_rx, keep_tx=keep_tx)
+            frames.append(bf.reshape(Isz[::-1] + (Nn, Vv)).permute(2, 1, 0, 3, 4))
+        b = torch.stack(frames, 3).reshape(Isz + Fsz + (Nn, Vv)) if frames else torch.zeros(Isz + Fsz + (Nn, Vv), dtype=torch.complex64, device=dev)
+        if not return_delays:
+            return (b, ksel) if return_bins else b
+        tt = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=dev)
+        Pg = tt(self.scan.positions())
+        ct = tt(cv if cv.size == 1 else cv.reshape(Isz)).reshape(Isz + (1,) if cv.size != 1 else (1, 1, 1, 1))
+        tau = lambda P: torch.linalg.norm(Pg[..., None] - tt(P)[:, None, None, None, :], dim=0) / ct
+        out = (b, tau(Pr), tau(Pt).unsqueeze(3), tau_foc)
+        return out + (ksel,) if return_bins else out
 
     def bfDASLUT(self, chd: ChannelData, tau_rx, tau_tx, *apods, apod=1, fmod=0.0, interp="cubic", keep_tx=False,
                  keep_rx=False, prec=None, bsize=None):
