@@ -143,6 +143,7 @@ extern "C" {
 #define QDAS_EHIP          3 /* HIP runtime error (message carries hipGetErrorString)   */
 #define QDAS_ENOMEM        4
 #define QDAS_ENOCONV       5 /* an iteration reached its pass cap without a fixed point  */
+#define QDAS_ENOTLDS       6 /* qdas_migration: a transform length its in-LDS kernels do not take (the caller composes the image instead) */
 
 /* Size/flag constants: the reference's constant-memory symbols QUPS_{T,N,M,I,I1,I2,I3,S},
  * QUPS_{VS,DV}, QUPS_BF_FLAG (reference src/sizes.cu:17-52, src/bf.cu:45-47;
@@ -565,6 +566,37 @@ typedef struct qdas_adjoint_desc {
     int32_t  device;              /* HIP device ordinal, -1 = current                 */
 } qdas_adjoint_desc;
 int qdas_adjoint(const qdas_adjoint_desc *desc, const void *X, void *b, void *stream);
+
+/* ---- Plane-wave Stolt f-k migration (migration.hip): the reference's bfMigration (src/UltrasoundSystem.m:4675-4887) as ONE call.
+ * Per transmit m of x[t, n, m, frame] (complex64, T x N x M x frames, time fastest), with transform lengths F (time) and K (lateral),
+ * f_j = (j - floor(F/2)) fs / F, kx_k = (k - floor(K/2)) / K / pitch, cs = c0 / sqrt(2):
+ *   1. x *= exp(2 pi i fmod (t0 + t / fs));  X = fftshift(FFT_t(x, F))            (zero-padded or truncated to F)
+ *   2. X *= exp(-2 pi i f (t0 + tau[n, m]))
+ *   3. X  = fftshift(FFT_n(X, K))                                                  (zero-padded or truncated to K)
+ *   4. y[j, k] = interp(X[:, k], kkz[j, k]),  kkz = sign(j0) sqrt(a^2 + j0^2) + floor(F/2),  j0 = j - floor(F/2),  a = kx cs F / fs
+ *      (fp64; the interpolators and the support rule of qdas_wsinterpd: all taps in [0, F) and kkz >= 0, else 0)
+ *   5. jacobian: y *= (f / cs) / (fkz + eps),  fkz = cs sign(f) sqrt(kx^2 + f^2 / cs^2)
+ *   6. y *= exp(+2 pi i f t0);  b = IFFT_t(ifftshift(y))
+ *   7. b *= exp(2 pi i kx gamma[m] z),  z = c0 / 2 (t0 + (0 : F-1) / fs)
+ *   8. b = IFFT_k(ifftshift(b));  9. crop to min(T, F) x min(N, K);  10. sum over m unless keep_tx (the sum is taken in front of step 8)
+ * b: DEVICE complex64 min(T,F) x min(N,K) x [M] x frames, time fastest.  tau (N x M, n fastest) and gamma (M) are DEVICE doubles.
+ * Four passes over an F x K x (block of transmits) work buffer, FFTs resident in LDS, no atomics: results are bit-reproducible.
+ * F and K must be lengths the in-LDS transforms take -- products of 2, 3, 5, 7, 11, 13 from 2 to 8192 whose stages fit a workgroup, and K <= 600 (two
+ * 16 x K tiles in LDS) -- otherwise QDAS_ENOTLDS and nothing is launched.  T, N, M or frames = 0: QDAS_OK, nothing is launched, no device needed.
+ * All validation happens on the host before any launch.  Work space comes from the stream's arena (below): the transmits are taken in blocks
+ * of at most 64 MiB (QDAS_MIGRATION_BLOCK_BYTES), so that no single piece is a hipMalloc of its own. */
+typedef struct qdas_migration_desc {
+    uint64_t T, N, M, frames;     /* samples, receivers, transmits, frames                          */
+    uint64_t F, K;                /* transform lengths in time and laterally                        */
+    double   fs, fmod, t0;        /* sampling frequency, modulation frequency, time of sample 0    */
+    double   c0, pitch;           /* sound speed, element pitch                                     */
+    int32_t  flag;                /* interpolator: 0 nearest, 1 linear, 2 cubic, 3 lanczos3, 5 cubic_dev */
+    int32_t  keep_tx, jacobian;   /* 0 | 1                                                          */
+    int32_t  device;              /* HIP device ordinal, -1 = current                               */
+    const double *tau;            /* N x M, n fastest: the sequence's delays at c0 [s]              */
+    const double *gamma;          /* M: sin(theta) / (2 - cos(theta))                               */
+} qdas_migration_desc;
+int qdas_migration(const qdas_migration_desc *desc, const void *x, void *b, void *stream);
 
 /* ---- Temporaries of the stream entries (qdas_shift_sum, qdas_das_lut, qdas_greens, qdas_convd's FFT path): taken from an arena the library keeps per (device,
  * stream).  One such call at a time runs per (device, stream) -- a second thread on the same stream waits --, and a call MAY BLOCK the host: when the stream's

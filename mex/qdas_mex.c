@@ -52,6 +52,8 @@
  * The frequency loop of bfAdjoint (src/UltrasoundSystem.m:3997-4037) as one call:
  *   b       = qdas_mex('adjoint', sizes, xk, f, Pi, Pr, Pt, cinv, del_tx, apod_tx, a_n, a_m, flags)
  *         sizes = [I N M V F], flags = [keep_rx keep_tx]; the arrays are described at cmd_adjoint below.  b is I x [N] x [V] single complex.
+ *   b       = qdas_mex('migration', sizes, x, tau, gamma, params, flags)
+ *         sizes = [T N M frames F K], params = [fs fmod t0 c0 pitch], flags = [interp keep_tx jacobian]; described at cmd_migration below.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
  * pass as device pointers and the result is a gpuArray.
  *
@@ -707,6 +709,38 @@ static mxArray *cmd_adjoint(int nrhs, const mxArray *prhs[]) {
     return finish(qdas_adjoint(&d, x, b, NULL), host, bytes);
 }
 
+/* b = qdas_mex('migration', sizes, x, tau, gamma, params, flags) -- bfMigration's loop over blocks of transmits (src/UltrasoundSystem.m:4801-4855).
+ * x: T x N x M x frames single complex, tau: N x M double (delays(seq, xdc) at c0), gamma: M double, params = [fs fmod t0 c0 pitch],
+ * flags = [interp keep_tx jacobian] (interp: 0 nearest, 1 linear, 2 cubic, 3 lanczos3, 5 cubic_dev).  b: min(T,F) x min(N,K) x [M] x frames single complex.
+ * Transform lengths the in-LDS kernels do not take raise QUPS:das_spec:qdas with the library's text (the caller composes the image in MATLAB then). */
+static mxArray *cmd_migration(int nrhs, const mxArray *prhs[]) {
+    if (nrhs != 6) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('migration', sizes, x, tau, gamma, params, flags)");
+    qdas_migration_desc d;
+    memset(&d, 0, sizeof d);
+    d.T = (uint64_t)num_at(prhs[0], 0, "sizes"); d.N = (uint64_t)num_at(prhs[0], 1, "sizes"); d.M = (uint64_t)num_at(prhs[0], 2, "sizes");
+    d.frames = (uint64_t)num_at(prhs[0], 3, "sizes"); d.F = (uint64_t)num_at(prhs[0], 4, "sizes"); d.K = (uint64_t)num_at(prhs[0], 5, "sizes");
+    d.fs = num_at(prhs[4], 0, "params"); d.fmod = num_at(prhs[4], 1, "params"); d.t0 = num_at(prhs[4], 2, "params");
+    d.c0 = num_at(prhs[4], 3, "params"); d.pitch = num_at(prhs[4], 4, "params");
+    d.flag = (int32_t)num_at(prhs[5], 0, "flags"); d.keep_tx = num_at(prhs[5], 1, "flags") != 0; d.jacobian = num_at(prhs[5], 2, "flags") != 0;
+    d.device = -1;
+    const mxArray *xa = prhs[1];
+    if (!mxIsEmpty(xa) && (mxGetClassID(xa) != mxSINGLE_CLASS || !mxIsComplex(xa)))
+        mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "migration: the data must be single complex.");
+    for (int k = 2; k <= 3; ++k)
+        if (!mxIsEmpty(prhs[k]) && (mxGetClassID(prhs[k]) != mxDOUBLE_CLASS || mxIsComplex(prhs[k]))) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "migration: tau and gamma must be real double.");
+    const uint64_t Tn = d.T < d.F ? d.T : d.F, Nn = d.N < d.K ? d.N : d.K;
+    const mwSize dims[4] = {(mwSize)Tn, (mwSize)Nn, (mwSize)(d.keep_tx ? d.M : 1), (mwSize)d.frames};
+    const size_t bytes = (size_t)dims[0] * dims[1] * dims[2] * dims[3] * 8;
+    if (!bytes || !d.M) return mxCreateNumericArray(4, dims, mxSINGLE_CLASS, mxCOMPLEX);           /* empty in, empty out */
+    int dev = 0;
+    const void *x = dev_in(xa, (size_t)(d.T * d.N * d.M * d.frames) * 8, "x", &dev);
+    d.tau = (const double *)dev_in(prhs[2], (size_t)(d.N * d.M) * 8, "tau", &dev);
+    d.gamma = (const double *)dev_in(prhs[3], (size_t)d.M * 8, "gamma", &dev);
+    mxArray *host;
+    void *b = dev_out(4, dims, mxSINGLE_CLASS, 1, dev, bytes, &host);
+    return finish(qdas_migration(&d, x, b, NULL), host, bytes);
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
 #ifdef QDAS_MEX_GPU
     mxInitGPU();
@@ -751,6 +785,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "slsc") || !strcmp(cmd, "dmas") || !strcmp(cmd, "cohfac") || !strcmp(cmd, "pcf")) { cmd_coherence(cmd, nlhs, plhs, nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "msfm")) { plhs[0] = cmd_msfm(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "adjoint")) { plhs[0] = cmd_adjoint(nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "migration")) { plhs[0] = cmd_migration(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();
         } else mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unknown command '%s'.", cmd);

@@ -26,6 +26,7 @@ QDAS_CONV_X_ONE_COLUMN, QDAS_CONV_X_ONE_SLICE, QDAS_CONV_Y_ONE_COLUMN, QDAS_CONV
 PLAN_NO_RECIPROCAL, PLAN_JIT, PLAN_COPY_INPUTS, PLAN_NO_MIRROR, PLAN_MIRROR_SLAB, PLAN_NO_FOLD, PLAN_APPROX_SYMMETRY, PLAN_PREFOLDED = 1, 2, 4, 8, 16, 32, 64, 128
 COH_SLSC_AVERAGE, COH_SLSC_ENSEMBLE, COH_DMAS, COH_COHFAC, COH_PCF = 1, 2, 3, 4, 5
 QDAS_ENOCONV = 5
+QDAS_ENOTLDS = 6
 RXAPOD_NONE, RXAPOD_ACCEPTANCE, RXAPOD_COSINE, RXAPOD_FNUMBER_PLANAR, RXAPOD_FNUMBER_ORIENTED = 0, 1, 2, 3, 4
 
 # every symbol include/qdas.h declares (tests check the library exports all of them)
@@ -35,7 +36,7 @@ SYMBOLS = (
     "qdas_plan_last_kernel_ms", "qdas_plan_create_sharded", "qdas_plan_execute_sharded", "qdas_plan_sharded_info", "qdas_plan_sharded_mirror",
     "qdas_plan_destroy_sharded", "qdas_DAS", "qdas_DASf", "qdas_DASh", "qdas_delays", "qdas_delaysf",
     "qdas_das_lut", "qdas_das_lut_last_kernel", "qdas_wsinterpd", "qdas_shift_sum", "qdas_greens", "qdas_convd", "qdas_convd_len", "qdas_permute3", "qdas_pre_plan_create", "qdas_pre_execute", "qdas_pre_plan_destroy", "qdas_pre_plan_one_pass", "qdas_last_error", "qdas_version", "qdas_device_malloc", "qdas_device_free", "qdas_device_trim", "qdas_device_copy", "qdas_iir", "qdas_device_info", "qdas_kernel_variant_build", "qdas_kernel_variant_prebuilt",
-    "qdas_coherence", "qdas_eikonal", "qdas_eikonal_tables", "qdas_eikonal_last_passes", "qdas_eikonal_pass_cap", "qdas_adjoint",
+    "qdas_coherence", "qdas_eikonal", "qdas_eikonal_tables", "qdas_eikonal_last_passes", "qdas_eikonal_pass_cap", "qdas_adjoint", "qdas_migration",
 )
 
 
@@ -122,6 +123,13 @@ class AdjointDesc(C.Structure):
                 ("keep_rx", C.c_int32), ("keep_tx", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32)]
 
 
+class MigrationDesc(C.Structure):
+    _fields_ = [("T", C.c_uint64), ("N", C.c_uint64), ("M", C.c_uint64), ("frames", C.c_uint64), ("F", C.c_uint64), ("K", C.c_uint64),
+                ("fs", C.c_double), ("fmod", C.c_double), ("t0", C.c_double), ("c0", C.c_double), ("pitch", C.c_double),
+                ("flag", C.c_int32), ("keep_tx", C.c_int32), ("jacobian", C.c_int32), ("device", C.c_int32),
+                ("tau", C.c_void_p), ("gamma", C.c_void_p)]
+
+
 class QdasError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libqdas error {code}: {msg}")
@@ -186,6 +194,7 @@ def lib():
     L.qdas_eikonal_pass_cap.argtypes = [C.c_uint64, C.c_uint64]
     L.qdas_eikonal_pass_cap.restype = C.c_uint32
     L.qdas_adjoint.argtypes = [C.POINTER(AdjointDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qdas_migration.argtypes = [C.POINTER(MigrationDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64
     L.qdas_shift_sum.argtypes = [C.POINTER(ShiftDesc), C.c_void_p, C.c_void_p, C.c_void_p]

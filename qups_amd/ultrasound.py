@@ -24,6 +24,8 @@ class Transducer:
     normals: np.ndarray
     fc: float = 5e6
     offset: np.ndarray = field(default_factory=lambda: np.zeros(3))
+    kind: str = "Transducer"            # the reference's class of the array: 'TransducerArray' (linear), 'TransducerConvex', or the generic base
+    pitch: float | None = None          # element spacing of a linear array
 
     @property
     def numel(self):
@@ -35,12 +37,12 @@ class Transducer:
     @staticmethod
     def linear(numel, pitch, fc=5e6, offset=(0.0, 0.0, 0.0)):          # reference src/TransducerArray.m:95-109
         p, n = G.linear_array(numel, pitch, offset)
-        return Transducer(p, n, fc, np.asarray(offset, float))
+        return Transducer(p, n, fc, np.asarray(offset, float), "TransducerArray", float(pitch))
 
     @staticmethod
     def convex(numel, radius, angular_pitch_deg, fc=3.7e6, offset=(0.0, 0.0, 0.0)):   # reference src/TransducerConvex.m:85-102
         p, n = G.convex_array(numel, radius, angular_pitch_deg, offset)
-        return Transducer(p, n, fc, np.asarray(offset, float))
+        return Transducer(p, n, fc, np.asarray(offset, float), "TransducerConvex")
 
 
 @dataclass
@@ -633,6 +635,65 @@ class UltrasoundSystem:
         tau = lambda P: torch.linalg.norm(Pg[..., None] - tt(P)[:, None, None, None, :], dim=0) / ct
         out = (b, tau(Pr), tau(Pt).unsqueeze(3), tau_foc)
         return out + (ksel,) if return_bins else out
+
+    def bfMigration(self, chd: ChannelData, Nfft=None, c0=None, fmod=0.0, keep_tx=False, interp="cubic", jacobian=True, bsize=None):
+        """``[b, bscan] = bfMigration(us, chd, [F, K], 'c0', c0, 'fmod', fc, 'keep_tx', tf, 'interp', method, 'jacobian', tf, 'bsize', B)`` (reference
+        ``src/UltrasoundSystem.m:4675-4887``): plane-wave Stolt f-k migration.  ``b`` is ``min(T,F) x min(N,K) x [M] x frames...`` complex64 on the
+        data's device; ``bscan`` is the ``Scan.cartesian`` it is defined on: ``x = x0 + pitch (0 : N'-1)``, ``z = offset_z + z(1) + mean(diff(z)) (0 : T'-1)``
+        with ``z = c0 / 2 (t0 + (0 : F-1) / fs)`` -- the reference's regularised axis.
+
+        Both are ALWAYS returned.  The reference's resampling of ``b`` onto ``us.scan`` when only one output is requested is deliberately not built:
+        it is an ``interp2`` of a complex image, which the reference itself warns against ("Resampling a complex image can produce artefacts").
+
+        ``Nfft = [F, K]`` (default ``[T, N]``) zero-pads or truncates.  Lengths the in-LDS kernels take (products of 2, 3, 5, 7, 11, 13 up to
+        8192, K up to 600) run ``qdas_migration`` (``qups_amd.migration.migrate``); any other length runs ``qups_amd.migration.compose`` (torch.fft
+        and ``wsinterpd``), whose transmit blocks ``bsize`` bounds; the library bounds its own work buffer.  complex64 data only.
+        A per-transmit ``t0`` raises: the transmits would land on different depth axes and their sum has no scan -- ``ChannelData.rectifyt0`` first."""
+        import warnings
+        import torch
+        from . import _lib, migration as MG
+        if not isinstance(chd, ChannelData):
+            raise DasError("bfMigration: chd must be one ChannelData")
+        if interp not in _lib.INTERP_FLAGS:
+            raise DasError("Interp option not recognized: " + str(interp))
+        if self.seq.type != "PW":
+            warnings.warn(f'Expected a Sequence of type "PW", but instead it was type "{self.seq.type}". Unexpected results may occur.')
+        if self.xdc.kind != "TransducerArray":
+            warnings.warn(f'Expected a TransducerArray but the Transducer is a {self.xdc.kind}". Unexpected results may occur.')
+        chd = chd.rectifyDims()
+        x = chd._torch_data()
+        if x.dtype != torch.complex64:
+            raise DasError(f"bfMigration: complex64 data only, got {str(x.dtype).replace('torch.', '')}")
+        if np.size(chd.t0) != 1:
+            raise DasError("bfMigration: t0 must be a scalar: transmits with different start times land on different depth axes -- "
+                           "resample them onto one with ChannelData.rectifyt0 first")
+        if x.ndim < 3:
+            x = x.reshape(tuple(x.shape) + (1,) * (3 - x.ndim))
+        T, N, M = (int(v) for v in x.shape[:3])
+        F, K = MG._nfft(Nfft, T, N)
+        if bsize is not None and (int(bsize) != bsize or bsize < 1):
+            raise DasError("bfMigration: bsize must be a positive integer")
+        if N != self.xdc.numel:
+            raise DasError("Number of receives must match number of receiver elements.")
+        c0 = float(self.seq.c0 if c0 is None else c0)
+        sq = Sequence(self.seq.type, self.seq.focus, c0, self.seq.numPulse)
+        tau = np.asarray(sq.delays(self.xdc), float)
+        if tau.shape != (N, M):
+            raise DasError(f"Number of transmits ({M}) must match the sequence's delays ({tau.shape[0]} x {tau.shape[1]}).")
+        pn = np.asarray(self.xdc.positions(), float)
+        pitch = self.xdc.pitch if self.xdc.pitch is not None else float(np.linalg.norm(pn[:, 1] - pn[:, 0]))
+        gam = MG.gamma(self.seq.focus) if self.seq.type == "PW" else np.zeros(M)
+        t0, fs = float(np.asarray(chd.t0, float).reshape(-1)[0]), float(chd.fs)
+        if not x.is_cuda:
+            if not torch.cuda.is_available():
+                raise RuntimeError("qups_amd: no HIP device visible -- the migration beamformer has no CPU fallback")
+            x = x.cuda()
+        b = MG.bmode(x, t0, fs, tau, gam, pitch, c0, (F, K), fmod, interp, jacobian, keep_tx, None if bsize is None else int(bsize))
+        Tn, Nn = min(T, F), min(N, K)
+        zax = c0 / 2.0 * (t0 + np.arange(F) / fs)
+        z = float(self.xdc.offset[2]) + zax[:Tn]
+        z = z[0] + (np.mean(np.diff(z)) if Tn > 1 else 0.0) * np.arange(Tn)
+        return b, Scan.cartesian(pn[0, 0] + pitch * np.arange(Nn), z, (float(self.xdc.offset[1]),))
 
     def bfDASLUT(self, chd: ChannelData, tau_rx, tau_tx, *apods, apod=1, fmod=0.0, interp="cubic", keep_tx=False,
                  keep_rx=False, prec=None, bsize=None):
