@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "../../include/qdas.h"
+#include "api_util.h"
 #include "qdas_kernels.h"
 
 namespace qdas {
@@ -268,16 +269,10 @@ __global__ void adj_keeprx(const Args a, const float2 *__restrict__ Ah, int keep
 }  // namespace adj
 }  // namespace qdas
 
-void qdas_internal_set_error(const char *msg);          // qdas_api.hip: the library's thread-local last-error string
-
-static int adj_fail(int rc, const char *msg) { qdas_internal_set_error(msg); return rc; }
+using qdas::fail;
+using qdas::DeviceGuard;
 
 namespace {
-struct AdjDeviceGuard {
-    int prev = -1;
-    bool set(int dev) { return dev < 0 || (hipGetDevice(&prev) == hipSuccess && hipSetDevice(dev) == hipSuccess); }
-    ~AdjDeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 // work space of one pixel block of the keep_tx / keep_rx forms: 256 MiB (QDAS_ADJOINT_BLOCK_BYTES, read per call: the tests make it small to see several blocks)
 size_t adj_block_bytes() { const char *e = getenv("QDAS_ADJOINT_BLOCK_BYTES"); return e && atoll(e) > 0 ? (size_t)atoll(e) : (size_t)256 << 20; }
 // workgroups wanted before the frequencies stop being split: 512 (QDAS_ADJOINT_FILL, read per call: the tests set it to see one chunk, or many)
@@ -294,28 +289,28 @@ unsigned adj_blocks(size_t total) { return (unsigned)std::min<size_t>((total + 2
 
 extern "C" int qdas_adjoint(const qdas_adjoint_desc *d, const void *X, void *b, void *stream) {
     using namespace qdas::adj;
-    if (!d) return adj_fail(QDAS_EINVAL, "adjoint: null descriptor");
-    if (d->dtype == QDAS_F16 || d->dtype == QDAS_F64) return adj_fail(QDAS_EUNSUPPORTED, "adjoint: complex64 data only (half precision is insufficient for frequency-domain beamforming; there is no fp64 path)");
-    if (d->dtype != QDAS_F32) return adj_fail(QDAS_EINVAL, "adjoint: unknown dtype");
-    if ((d->keep_rx != 0 && d->keep_rx != 1) || (d->keep_tx != 0 && d->keep_tx != 1)) return adj_fail(QDAS_EINVAL, "adjoint: keep_rx and keep_tx are 0 or 1");
+    if (!d) return fail(QDAS_EINVAL, "adjoint: null descriptor");
+    if (d->dtype == QDAS_F16 || d->dtype == QDAS_F64) return fail(QDAS_EUNSUPPORTED, "adjoint: complex64 data only (half precision is insufficient for frequency-domain beamforming; there is no fp64 path)");
+    if (d->dtype != QDAS_F32) return fail(QDAS_EINVAL, "adjoint: unknown dtype");
+    if ((d->keep_rx != 0 && d->keep_rx != 1) || (d->keep_tx != 0 && d->keep_tx != 1)) return fail(QDAS_EINVAL, "adjoint: keep_rx and keep_tx are 0 or 1");
     const uint64_t LIM = 0x7fffff00ull;
-    if (d->I > LIM || d->N > LIM || d->M > LIM || d->V > LIM || d->Ksel > LIM) return adj_fail(QDAS_EUNSUPPORTED, "adjoint: every extent is at most 2^31 - 256");
-    if (d->cinv_count != 1 && d->cinv_count != d->I) return adj_fail(QDAS_EINVAL, "adjoint: cinv holds 1 or I values");
+    if (d->I > LIM || d->N > LIM || d->M > LIM || d->V > LIM || d->Ksel > LIM) return fail(QDAS_EUNSUPPORTED, "adjoint: every extent is at most 2^31 - 256");
+    if (d->cinv_count != 1 && d->cinv_count != d->I) return fail(QDAS_EINVAL, "adjoint: cinv holds 1 or I values");
     if (d->I == 0 || (d->keep_rx && d->N == 0) || (d->keep_tx && d->V == 0)) return QDAS_OK;          // b has no elements: nothing is launched
-    if (!b) return adj_fail(QDAS_EINVAL, "adjoint: null output pointer");
-    AdjDeviceGuard guard;
-    if (!guard.set(d->device)) return adj_fail(QDAS_EHIP, "hipSetDevice failed");
+    if (!b) return fail(QDAS_EINVAL, "adjoint: null output pointer");
+    DeviceGuard guard(d->device);
+    if (guard.err != hipSuccess) return fail(QDAS_EHIP, "hipSetDevice failed");
     const hipStream_t s = (hipStream_t)stream;
     const size_t nout = (size_t)d->I * (d->keep_rx ? d->N : 1) * (d->keep_tx ? d->V : 1);
     if (d->N == 0 || d->V == 0 || d->Ksel == 0) {           // an empty sum: zeros, no kernel
         const hipError_t e = hipMemsetAsync(b, 0, nout * sizeof(float2), s);
-        return e == hipSuccess ? QDAS_OK : adj_fail(QDAS_EHIP, hipGetErrorString(e));
+        return e == hipSuccess ? QDAS_OK : fail(QDAS_EHIP, "%s", hipGetErrorString(e));
     }
-    if (d->M == 0) return adj_fail(QDAS_EINVAL, "adjoint: no transmit elements (M = 0): the transmit field has no norm");
-    if (!X || !d->Pi || !d->Pr || !d->Pt || !d->cinv || !d->freq || !d->del_tx || !d->apod_tx) return adj_fail(QDAS_EINVAL, "adjoint: null data pointer");
+    if (d->M == 0) return fail(QDAS_EINVAL, "adjoint: no transmit elements (M = 0): the transmit field has no norm");
+    if (!X || !d->Pi || !d->Pr || !d->Pt || !d->cinv || !d->freq || !d->del_tx || !d->apod_tx) return fail(QDAS_EINVAL, "adjoint: null data pointer");
     const uint32_t I = (uint32_t)d->I, N = (uint32_t)d->N, M = (uint32_t)d->M, V = (uint32_t)d->V, K = (uint32_t)d->Ksel;
     const uint32_t VG = V <= 32 ? 32 : 64, nvg = (V + VG - 1) / VG;
-    if (nvg > 65535) return adj_fail(QDAS_EUNSUPPORTED, "adjoint: at most 65535 x 64 transmits");
+    if (nvg > 65535) return fail(QDAS_EUNSUPPORTED, "adjoint: at most 65535 x 64 transmits");
 
     // the pixels of one launch: all of them for the summed image; blocks under the work-space budget for the kept forms
     const size_t per_pixel = d->keep_rx ? (size_t)K * V * sizeof(float2) : (d->keep_tx ? (size_t)K * sizeof(float) : 0);
@@ -335,8 +330,8 @@ extern "C" int qdas_adjoint(const qdas_adjoint_desc *d, const void *X, void *b, 
     char *w0 = (char *)scratch.get(off_S + nS * sizeof(float2));
     const bool partial = !d->keep_rx && !d->keep_tx && kchunks > 1;
     void *w1 = per_pixel ? scratch.get(per_pixel * IB) : (partial ? scratch.get((size_t)kchunks * I * sizeof(float2)) : nullptr);
-    if (!w0 || ((per_pixel || partial) && !w1)) return adj_fail(QDAS_ENOMEM, "adjoint: no memory for the work space");
-    auto hip_fail = [&](hipError_t e) { (void)hipStreamSynchronize(s); return adj_fail(QDAS_EHIP, hipGetErrorString(e)); };
+    if (!w0 || ((per_pixel || partial) && !w1)) return fail(QDAS_ENOMEM, "adjoint: no memory for the work space");
+    auto hip_fail = [&](hipError_t e) { (void)hipStreamSynchronize(s); return fail(QDAS_EHIP, "%s", hipGetErrorString(e)); };
     hipError_t e = hipMemcpyAsync(w0, d->freq, (size_t)K * sizeof(double), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return hip_fail(e);
 

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "../../include/qdas.h"
+#include "api_util.h"
 
 namespace qdas {
 namespace coh {
@@ -313,24 +314,22 @@ static void launch(int method, int dmas_all, const Params &P, hipStream_t s) {
 }  // namespace coh
 }  // namespace qdas
 
-void qdas_internal_set_error(const char *msg);          // qdas_api.hip: the library's thread-local last-error string
-
-static int coh_fail(int rc, const char *msg) { qdas_internal_set_error(msg); return rc; }
+using qdas::fail;
 
 extern "C" int qdas_coherence(const qdas_coherence_desc *d, const void *x, void *y, void *y2, void *stream) {
     using namespace qdas::coh;
-    if (!d) return coh_fail(QDAS_EINVAL, "coherence: null descriptor");
-    if (d->method < QDAS_COH_SLSC_AVERAGE || d->method > QDAS_COH_PCF) return coh_fail(QDAS_EINVAL, "coherence: unknown method");
-    if (d->dtype != QDAS_F64 && d->dtype != QDAS_F32) return coh_fail(QDAS_EINVAL, "coherence: datatype must be double or single");
-    if (d->N == 0) return coh_fail(QDAS_EINVAL, "coherence: the aperture dimension is empty (N = 0)");
+    if (!d) return fail(QDAS_EINVAL, "coherence: null descriptor");
+    if (d->method < QDAS_COH_SLSC_AVERAGE || d->method > QDAS_COH_PCF) return fail(QDAS_EINVAL, "coherence: unknown method");
+    if (d->dtype != QDAS_F64 && d->dtype != QDAS_F32) return fail(QDAS_EINVAL, "coherence: datatype must be double or single");
+    if (d->N == 0) return fail(QDAS_EINVAL, "coherence: the aperture dimension is empty (N = 0)");
     const uint64_t K = d->K ? d->K : 1;
-    if (d->method == QDAS_COH_PCF && !d->cplx) return coh_fail(QDAS_EINVAL, "pcf: Input must be complex.");
-    if (d->method == QDAS_COH_PCF && K != 1) return coh_fail(QDAS_EINVAL, "pcf: one reduced dimension (K = 1)");
-    if (d->method == QDAS_COH_DMAS && K != 1) return coh_fail(QDAS_EINVAL, "dmas: one reduced dimension (K = 1)");
+    if (d->method == QDAS_COH_PCF && !d->cplx) return fail(QDAS_EINVAL, "pcf: Input must be complex.");
+    if (d->method == QDAS_COH_PCF && K != 1) return fail(QDAS_EINVAL, "pcf: one reduced dimension (K = 1)");
+    if (d->method == QDAS_COH_DMAS && K != 1) return fail(QDAS_EINVAL, "dmas: one reduced dimension (K = 1)");
     uint64_t P = 1, sz[3];
     for (int i = 0; i < 3; ++i) { sz[i] = d->size[i]; P *= sz[i]; }   // (a size of 0 is an empty image: nothing is launched)
     if (d->N >= (1ull << 31) || K >= (1ull << 31) || P >= (1ull << 32) || sz[0] >= (1ull << 32) || sz[1] >= (1ull << 32))
-        return coh_fail(QDAS_EUNSUPPORTED, "coherence: at most 2^32 - 1 pixels and 2^31 - 1 receivers per call");
+        return fail(QDAS_EUNSUPPORTED, "coherence: at most 2^32 - 1 pixels and 2^31 - 1 receivers per call");
 
     Params p;
     memset(&p, 0, sizeof p);
@@ -343,7 +342,7 @@ extern "C" int qdas_coherence(const qdas_coherence_desc *d, const void *x, void 
         const bool slsc = d->method != QDAS_COH_DMAS;
         const uint64_t top = d->N - 1;                   // largest lag with pairs
         if (!d->lags) {                                  // the range [lag_lo, lag_hi]
-            if (d->lag_hi < d->lag_lo) { if (slsc) return coh_fail(QDAS_EINVAL, "slsc: empty lag set"); }
+            if (d->lag_hi < d->lag_lo) { if (slsc) return fail(QDAS_EINVAL, "slsc: empty lag set"); }
             else {
                 p.lnorm = (double)(d->lag_hi - d->lag_lo + 1);
                 p.zero_lag = slsc && d->lag_lo == 0;
@@ -353,14 +352,14 @@ extern "C" int qdas_coherence(const qdas_coherence_desc *d, const void *x, void 
                 p.ntot = p.maxlag ? p.hi - p.lo + 1 : 0;
             }
         } else {                                         // a table: ismember / intersect semantics, duplicates only count in L
-            if (d->nlags == 0) { if (slsc) return coh_fail(QDAS_EINVAL, "slsc: empty lag set"); }
+            if (d->nlags == 0) { if (slsc) return fail(QDAS_EINVAL, "slsc: empty lag set"); }
             p.lnorm = (double)d->nlags;
             for (uint64_t i = 0; i < d->nlags; ++i) {
                 const int64_t l = d->lags[i];
-                if (l < 0) return coh_fail(QDAS_EINVAL, "coherence: lags must be non-negative");
+                if (l < 0) return fail(QDAS_EINVAL, "coherence: lags must be non-negative");
                 if (l == 0) { p.zero_lag = slsc; continue; }
                 if ((uint64_t)l > top) continue;
-                if ((uint64_t)l >= MASK_LAGS) return coh_fail(QDAS_EUNSUPPORTED, "coherence: a lag table reaches at most lag 2047 (a range has no limit)");
+                if ((uint64_t)l >= MASK_LAGS) return fail(QDAS_EUNSUPPORTED, "coherence: a lag table reaches at most lag 2047 (a range has no limit)");
                 p.mask[l >> 5] |= 1u << (l & 31);
                 if ((uint32_t)l > p.maxlag) p.maxlag = (uint32_t)l;
             }
@@ -373,15 +372,15 @@ extern "C" int qdas_coherence(const qdas_coherence_desc *d, const void *x, void 
         }
     }
     if (P == 0) return QDAS_OK;
-    if (!x || !y || (d->method == QDAS_COH_PCF && !y2)) return coh_fail(QDAS_EINVAL, "coherence: null data pointer");
+    if (!x || !y || (d->method == QDAS_COH_PCF && !y2)) return fail(QDAS_EINVAL, "coherence: null data pointer");
     p.x = x; p.y = y; p.y2 = y2;
     int prev = -1;
-    if (d->device >= 0) { if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(d->device) != hipSuccess) return coh_fail(QDAS_EHIP, "hipSetDevice failed"); }
+    if (d->device >= 0) { if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(d->device) != hipSuccess) return fail(QDAS_EHIP, "hipSetDevice failed"); }
     const hipStream_t s = (hipStream_t)stream;
     if (d->dtype == QDAS_F32) { if (d->cplx) launch<float, true>(d->method, dmas_all, p, s); else launch<float, false>(d->method, dmas_all, p, s); }
     else                      { if (d->cplx) launch<double, true>(d->method, dmas_all, p, s); else launch<double, false>(d->method, dmas_all, p, s); }
     const hipError_t e = hipGetLastError();
     if (prev >= 0) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return coh_fail(QDAS_EHIP, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(QDAS_EHIP, "%s", hipGetErrorString(e));
     return QDAS_OK;
 }

@@ -23,7 +23,8 @@
 #include <type_traits>
 #include "qdas_device.h"
 #include "qdas_kernels.h"
-#include "../../include/qdas.h"
+#include "api_util.h"
+#include <stdlib.h>
 
 namespace qdas {
 
@@ -264,3 +265,56 @@ hipError_t launch_conv(const ConvParams &P, int dtype, int cplx, int y_real, hip
 }
 
 }  // namespace qdas
+
+using namespace qdas;
+
+extern "C" uint64_t qdas_convd_len(uint64_t M, uint64_t N, int shape) {
+    if (M == 0 || N == 0) return 0;
+    switch (shape) {
+        case QDAS_CONV_FULL:  return M + N - 1;
+        case QDAS_CONV_SAME:  return M;
+        case QDAS_CONV_VALID: return M >= N ? M - N + 1 : 0;
+        case QDAS_CONV_CAUSAL: return M;
+        default: return 0;
+    }
+}
+
+extern "C" int qdas_convd(const qdas_convd_desc *d, const void *x, const void *y, void *z, void *stream) {
+    if (!d) return fail(QDAS_EINVAL, "null argument");
+    if (d->dtype != QDAS_F64 && d->dtype != QDAS_F32 && d->dtype != QDAS_F16) return fail(QDAS_EINVAL, "convd: datatype must be double, single or half");
+    if (d->shape != QDAS_CONV_FULL && d->shape != QDAS_CONV_SAME && d->shape != QDAS_CONV_VALID && d->shape != QDAS_CONV_CAUSAL)
+        return fail(QDAS_EINVAL, "convd: shape must be one of {'full', 'same', 'valid'}");
+    if (d->bcast & ~15) return fail(QDAS_EINVAL, "convd: unknown broadcast bits");
+    if (d->y_real && !d->cplx) return fail(QDAS_EINVAL, "convd: y_real describes complex data with real taps (cplx must be 1)");
+    if (d->M >= (1ull << 31) || d->N >= (1ull << 31)) return fail(QDAS_EUNSUPPORTED, "convd: at most 2^31 - 1 samples along the convolved dimension");
+    const uint64_t L = qdas_convd_len(d->M, d->N, d->shape);
+    if (L == 0 || d->C == 0 || d->S == 0) return QDAS_OK;
+    if (!x || !y || !z) return fail(QDAS_EINVAL, "null data pointer");
+    const uint64_t ncb = (d->C + 63) / 64;
+    if (d->S * (d->C == 1 ? 1 : ncb) >= (1ull << 31) || (L + 15) / 16 > 65535ull * (d->C == 1 ? 64 : 1))
+        return fail(QDAS_EUNSUPPORTED, "convd: too many slices / outputs for one launch");
+    DeviceGuard guard(d->device);
+    HIPCHK(guard.err);
+    ConvParams p{};
+    p.x = x; p.y = y; p.z = z;
+    p.C = d->C; p.M = d->M; p.N = d->N; p.L = L; p.S = d->S;
+    p.off = (d->shape == QDAS_CONV_FULL || d->shape == QDAS_CONV_CAUSAL) ? 0 : d->shape == QDAS_CONV_VALID ? (int64_t)d->N - 1 : (int64_t)(d->N - 1 - (d->N - 1) / 2);
+    const uint64_t Cx = (d->bcast & QDAS_CONV_X_ONE_COLUMN) ? 1 : d->C, Cy = (d->bcast & QDAS_CONV_Y_ONE_COLUMN) ? 1 : d->C;
+    p.xcs = Cx == 1 && d->C > 1 ? 0 : 1; p.xts = Cx; p.xss = (d->bcast & QDAS_CONV_X_ONE_SLICE) ? 0 : Cx * d->M;
+    p.ycs = Cy == 1 && d->C > 1 ? 0 : 1; p.yts = Cy; p.yss = (d->bcast & QDAS_CONV_Y_ONE_SLICE) ? 0 : Cy * d->N;
+    // long filters on complex64 traces, ONE filter for all of them, time contiguous (ChannelData.filter's band-pass): FFT convolution with the trace
+    // resident in LDS (pre.hip fftconv_launch) -- from QDAS_CONV_FFT_MIN_TAPS taps on (default 128: it overtakes the direct kernel at about 120 taps on the C3 record, profiles/r04/convd_fft_time.txt)
+    {
+        static const bool no_fft = getenv("QDAS_CONV_NO_FFT") != nullptr;
+        uint64_t min_taps = 128;
+        if (const char *e = getenv("QDAS_CONV_FFT_MIN_TAPS")) { const long long v = atoll(e); if (v >= 2) min_taps = (uint64_t)v; }
+        const bool one_filter = d->S == 1 || (d->bcast & QDAS_CONV_Y_ONE_SLICE), every_trace = d->S == 1 || !(d->bcast & QDAS_CONV_X_ONE_SLICE);
+        if (!no_fft && d->dtype == QDAS_F32 && d->cplx && d->C == 1 && one_filter && every_trace && d->N >= min_taps) {
+            const int rc = fftconv_launch(x, y, d->y_real ? 1 : 0, z, d->M, d->N, d->S, (uint64_t)p.off, L, (hipStream_t)stream);
+            if (rc == 0) return QDAS_OK;
+            if (rc == 2) return fail(QDAS_EHIP, "convd: the FFT convolution kernel failed to launch");
+        }
+    }
+    HIPCHK(launch_conv(p, d->dtype, d->cplx ? 1 : 0, d->y_real ? 1 : 0, (hipStream_t)stream));
+    return QDAS_OK;
+}

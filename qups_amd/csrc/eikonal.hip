@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/qdas.h"
+#include "api_util.h"
 #include "qdas_kernels.h"
 
 namespace qdas {
@@ -189,9 +190,8 @@ __global__ void __launch_bounds__(256) tables_kernel(const double *__restrict__ 
 }  // namespace eik
 }  // namespace qdas
 
-void qdas_internal_set_error(const char *msg);          // qdas_api.hip: the library's thread-local last-error string
-
-static int eik_fail(int rc, const char *msg) { qdas_internal_set_error(msg); return rc; }
+using qdas::fail;
+using qdas::DeviceGuard;
 static thread_local int g_eik_passes = 0;
 
 extern "C" int qdas_eikonal_last_passes(void) { return g_eik_passes; }
@@ -201,20 +201,12 @@ extern "C" uint32_t qdas_eikonal_pass_cap(uint64_t C1, uint64_t C2) {
     return cap > 0x7fffffffull ? 0x7fffffffu : (uint32_t)cap;
 }
 
-namespace {
-struct DeviceGuard {
-    int prev = -1;
-    bool set(int dev) { return dev < 0 || (hipGetDevice(&prev) == hipSuccess && hipSetDevice(dev) == hipSuccess); }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-}  // namespace
-
 static int eik_check_grid(const qdas_eikonal_desc *d) {
-    if (!d) return eik_fail(QDAS_EINVAL, "eikonal: null descriptor");
-    if (d->C1 >= (1ull << 31) || d->C2 >= (1ull << 31) || d->C1 * d->C2 >= (1ull << 32)) return eik_fail(QDAS_EUNSUPPORTED, "eikonal: at most 2^32 - 1 nodes per map");
-    if (d->K > 65535) return eik_fail(QDAS_EUNSUPPORTED, "eikonal: at most 65535 source sets per call");
-    if (((d->C1 + 15) / 16) * ((d->C2 + 15) / 16) >= (1ull << 24)) return eik_fail(QDAS_EUNSUPPORTED, "eikonal: at most 2^24 - 1 tiles of 16 x 16 nodes per map (one launch covers them)");
-    if (d->base != 0 && d->base != 1) return eik_fail(QDAS_EINVAL, "eikonal: coordinates are 0- or 1-based");
+    if (!d) return fail(QDAS_EINVAL, "eikonal: null descriptor");
+    if (d->C1 >= (1ull << 31) || d->C2 >= (1ull << 31) || d->C1 * d->C2 >= (1ull << 32)) return fail(QDAS_EUNSUPPORTED, "eikonal: at most 2^32 - 1 nodes per map");
+    if (d->K > 65535) return fail(QDAS_EUNSUPPORTED, "eikonal: at most 65535 source sets per call");
+    if (((d->C1 + 15) / 16) * ((d->C2 + 15) / 16) >= (1ull << 24)) return fail(QDAS_EUNSUPPORTED, "eikonal: at most 2^24 - 1 tiles of 16 x 16 nodes per map (one launch covers them)");
+    if (d->base != 0 && d->base != 1) return fail(QDAS_EINVAL, "eikonal: coordinates are 0- or 1-based");
     return QDAS_OK;
 }
 
@@ -222,28 +214,28 @@ extern "C" int qdas_eikonal(const qdas_eikonal_desc *d, const double *c, const d
     using namespace qdas::eik;
     g_eik_passes = 0;
     if (int rc = eik_check_grid(d)) return rc;
-    if (d->set_begin ? false : d->npts != d->K) return eik_fail(QDAS_EINVAL, "eikonal: without set_begin every source set is one point (npts == K)");
-    if (!(d->dp > 0.0) || !std::isfinite(d->dp)) return eik_fail(QDAS_EINVAL, "eikonal: the grid step must be positive");
+    if (d->set_begin ? false : d->npts != d->K) return fail(QDAS_EINVAL, "eikonal: without set_begin every source set is one point (npts == K)");
+    if (!(d->dp > 0.0) || !std::isfinite(d->dp)) return fail(QDAS_EINVAL, "eikonal: the grid step must be positive");
     const uint64_t CC = d->C1 * d->C2;
     if (CC == 0 || d->K == 0) return QDAS_OK;            // an empty grid or no sources: nothing is launched
-    if (!c || !src || !T) return eik_fail(QDAS_EINVAL, "eikonal: null data pointer");
+    if (!c || !src || !T) return fail(QDAS_EINVAL, "eikonal: null data pointer");
     const uint32_t C1 = (uint32_t)d->C1, C2 = (uint32_t)d->C2, K = (uint32_t)d->K;
     // source points: floored to a node (kern/msfm2d.m:97), every one inside the grid (kern/msfm.m:96-99)
     std::vector<uint2> pts;
     pts.reserve(d->npts);
     for (uint32_t k = 0; k < K; ++k) {
         const uint64_t b = d->set_begin ? d->set_begin[k] : k, e = d->set_begin ? d->set_begin[k + 1] : k + 1;
-        if (e < b || e > d->npts) return eik_fail(QDAS_EINVAL, "eikonal: set_begin must ascend and end at npts");
-        if (e == b) return eik_fail(QDAS_EINVAL, "eikonal: a source set is empty");
+        if (e < b || e > d->npts) return fail(QDAS_EINVAL, "eikonal: set_begin must ascend and end at npts");
+        if (e == b) return fail(QDAS_EINVAL, "eikonal: a source set is empty");
         for (uint64_t p = b; p < e; ++p) {
             const double u = src[2 * p] - d->base, v = src[2 * p + 1] - d->base;
-            if (!(u >= 0.0 && v >= 0.0 && u <= (double)(C1 - 1) && v <= (double)(C2 - 1))) return eik_fail(QDAS_EINVAL, "eikonal: a source point lies outside the grid");
+            if (!(u >= 0.0 && v >= 0.0 && u <= (double)(C1 - 1) && v <= (double)(C2 - 1))) return fail(QDAS_EINVAL, "eikonal: a source point lies outside the grid");
             pts.push_back(make_uint2((uint32_t)floor(v) * C1 + (uint32_t)floor(u), k));
         }
     }
     const uint32_t cap = d->max_passes ? d->max_passes : qdas_eikonal_pass_cap(C1, C2);
-    DeviceGuard guard;
-    if (!guard.set(d->device)) return eik_fail(QDAS_EHIP, "hipSetDevice failed");
+    DeviceGuard guard(d->device);
+    if (guard.err != hipSuccess) return fail(QDAS_EHIP, "hipSetDevice failed");
     const hipStream_t s = (hipStream_t)stream;
     const uint32_t tiles1 = (C1 + TS - 1) / TS, tiles2 = (C2 + TS - 1) / TS, ntiles = tiles1 * tiles2;
     const size_t nflag = (size_t)K * ntiles;
@@ -252,10 +244,10 @@ extern "C" int qdas_eikonal(const qdas_eikonal_desc *d, const double *c, const d
     static_assert(CHUNK <= 8, "the counters of a chunk");
     qdas::Scratch scratch(s);
     char *ws = (char *)scratch.get(bytes);
-    if (!ws) return eik_fail(QDAS_ENOMEM, "eikonal: no memory for the work space");
+    if (!ws) return fail(QDAS_ENOMEM, "eikonal: no memory for the work space");
     int *flags = (int *)ws, *counters = (int *)(ws + off_cnt);
     uint2 *dpts = (uint2 *)(ws + off_pts);
-    auto hip_fail = [&](hipError_t e) { (void)hipStreamSynchronize(s); return eik_fail(QDAS_EHIP, hipGetErrorString(e)); };
+    auto hip_fail = [&](hipError_t e) { (void)hipStreamSynchronize(s); return fail(QDAS_EHIP, "%s", hipGetErrorString(e)); };
     hipError_t e = hipMemsetAsync(ws, 0, off_pts, s);
     if (e == hipSuccess) e = hipMemcpyAsync(dpts, pts.data(), pts.size() * sizeof(uint2), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return hip_fail(e);
@@ -276,7 +268,7 @@ extern "C" int qdas_eikonal(const qdas_eikonal_desc *d, const double *c, const d
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e);
         e = hipMemcpyAsync(host_cnt, counters, n * sizeof(int), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return eik_fail(QDAS_EHIP, hipGetErrorString(e));
+        if (e != hipSuccess) return fail(QDAS_EHIP, "%s", hipGetErrorString(e));
         for (uint32_t q = 0; q < n && !converged; ++q)
             if (host_cnt[q] == 0) { converged = true; g_eik_passes = (int)(done + q + 1); }
         done += n;
@@ -285,9 +277,7 @@ extern "C" int qdas_eikonal(const qdas_eikonal_desc *d, const double *c, const d
         g_eik_passes = (int)done;
         fill_kernel<<<(unsigned)std::min<size_t>((ntot + 255) / 256, 65536), 256, 0, s>>>(T, ntot, NAN);
         (void)hipStreamSynchronize(s);
-        char msg[160];
-        snprintf(msg, sizeof msg, "eikonal: no fixed point within %u passes (the map is set to NaN)", cap);
-        return eik_fail(QDAS_ENOCONV, msg);
+        return fail(QDAS_ENOCONV, "eikonal: no fixed point within %u passes (the map is set to NaN)", cap);
     }
     return QDAS_OK;
 }
@@ -295,14 +285,14 @@ extern "C" int qdas_eikonal(const qdas_eikonal_desc *d, const double *c, const d
 extern "C" int qdas_eikonal_tables(const qdas_eikonal_desc *d, const double *T, const double *Pi, double *tau, void *stream) {
     using namespace qdas::eik;
     if (int rc = eik_check_grid(d)) return rc;
-    if (d->I > 0xffffff00ull) return eik_fail(QDAS_EUNSUPPORTED, "eikonal: at most 2^32 - 256 pixels per call (one launch covers them)");
+    if (d->I > 0xffffff00ull) return fail(QDAS_EUNSUPPORTED, "eikonal: at most 2^32 - 256 pixels per call (one launch covers them)");
     if (d->I == 0 || d->K == 0) return QDAS_OK;
-    if (d->C1 * d->C2 == 0) return eik_fail(QDAS_EINVAL, "eikonal: tables of an empty grid");
-    if (!T || !Pi || !tau) return eik_fail(QDAS_EINVAL, "eikonal: null data pointer");
-    DeviceGuard guard;
-    if (!guard.set(d->device)) return eik_fail(QDAS_EHIP, "hipSetDevice failed");
+    if (d->C1 * d->C2 == 0) return fail(QDAS_EINVAL, "eikonal: tables of an empty grid");
+    if (!T || !Pi || !tau) return fail(QDAS_EINVAL, "eikonal: null data pointer");
+    DeviceGuard guard(d->device);
+    if (guard.err != hipSuccess) return fail(QDAS_EHIP, "hipSetDevice failed");
     tables_kernel<<<dim3((unsigned)((d->I + 255) / 256), (unsigned)d->K), 256, 0, (hipStream_t)stream>>>(T, Pi, tau, d->I, (uint32_t)d->C1, (uint32_t)d->C2, (double)d->base);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return eik_fail(QDAS_EHIP, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(QDAS_EHIP, "%s", hipGetErrorString(e));
     return QDAS_OK;
 }

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/qdas.h"
+#include "api_util.h"
 
 namespace qdas {
 
@@ -87,8 +88,6 @@ hipError_t launch_iir(const IirParams &P, int dtype, int cplx, hipStream_t s) {
 }
 
 }  // namespace qdas
-
-void qdas_internal_set_error(const char *msg);          // qdas_api.hip: the library's thread-local last-error string
 
 extern "C" int qdas_iir(const qdas_iir_desc *d, const void *x, void *y, void *stream) {
     if (!d) { qdas_internal_set_error("null argument"); return QDAS_EINVAL; }

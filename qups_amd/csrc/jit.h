@@ -43,5 +43,7 @@ std::string jit_compile(const JitSpec &k, std::vector<char> *code, std::string *
 struct JitKernel { hipFunction_t fn; std::string key, err; };
 JitKernel jit_kernel(JitSpec &k, int device);
 hipError_t jit_launch(hipFunction_t fn, const TileParams &P, unsigned grid, unsigned block, size_t lds, hipStream_t s);
+// dynamic LDS of a plan-specialised build (tN, tM: stage / block elements; act_bytes: the stage list of pixel weights; wtab: a staged weight table)
+size_t jit_tile_lds(const JitSpec &k, uint64_t tN, uint64_t tM, uint32_t act_bytes, bool wtab);
 
 }  // namespace qdas

@@ -4,6 +4,7 @@
 // reads coalesced along c, writes coalesced along a.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "api_util.h"
 
 namespace qdas {
 
@@ -41,3 +42,14 @@ hipError_t launch_permute3(const void *in, void *out, uint64_t A, uint64_t B, ui
 }
 
 }  // namespace qdas
+
+using namespace qdas;
+
+extern "C" int qdas_permute3(const void *in, void *out, uint64_t A, uint64_t B, uint64_t C, int elem_bytes, void *stream) {
+    if (A == 0 || B == 0 || C == 0) return QDAS_OK;
+    if (!in || !out) return fail(QDAS_EINVAL, "null argument");
+    if (elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8 && elem_bytes != 16) return fail(QDAS_EINVAL, "permute3: element size must be 2, 4, 8 or 16 bytes");
+    if (B > 65535 || (A + 63) / 64 > 65535) return fail(QDAS_EUNSUPPORTED, "permute3: too many slices for one launch");
+    HIPCHK(launch_permute3(in, out, A, B, C, elem_bytes, (hipStream_t)stream));
+    return QDAS_OK;
+}

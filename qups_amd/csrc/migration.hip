@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "../../include/qdas.h"
+#include "api_util.h"
 #include "qdas_kernels.h"
 #include "qdas_device.h"
 #include "fft_lds.h"
@@ -334,15 +335,7 @@ template <bool BIG> MigFn stolt_fn(int flag) {
 }  // namespace mig
 }  // namespace qdas
 
-void qdas_internal_set_error(const char *msg);          // qdas_api.hip: the library's thread-local last-error string
-
 namespace {
-int mig_fail(int rc, const char *msg) { qdas_internal_set_error(msg); return rc; }
-struct MigDeviceGuard {
-    int prev = -1;
-    bool set(int dev) { return dev < 0 || (hipGetDevice(&prev) == hipSuccess && hipSetDevice(dev) == hipSuccess); }
-    ~MigDeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 // bytes of the F x K x (transmits) work buffer of one block (QDAS_MIGRATION_BLOCK_BYTES, read per call: the tests make it small to see several blocks)
 size_t mig_block_bytes() { const char *e = getenv("QDAS_MIGRATION_BLOCK_BYTES"); return e && atoll(e) > 0 ? (size_t)atoll(e) : (size_t)64 << 20; }
 // workgroups pass C wants before the block's transmits stop being split into slices (QDAS_MIGRATION_FILL, read per call)
@@ -353,26 +346,26 @@ bool finite_pos(double v) { return v > 0.0 && v < INFINITY; }
 extern "C" int qdas_migration(const qdas_migration_desc *d, const void *x, void *b, void *stream) {
     using namespace qdas;
     using namespace qdas::mig;
-    if (!d) return mig_fail(QDAS_EINVAL, "migration: null descriptor");
-    if (d->flag != 0 && d->flag != 1 && d->flag != 2 && d->flag != 3 && d->flag != 5) return mig_fail(QDAS_EINVAL, "migration: unknown interpolator flag (0 nearest, 1 linear, 2 cubic, 3 lanczos3, 5 cubic_dev)");
-    if ((d->keep_tx != 0 && d->keep_tx != 1) || (d->jacobian != 0 && d->jacobian != 1)) return mig_fail(QDAS_EINVAL, "migration: keep_tx and jacobian are 0 or 1");
+    if (!d) return fail(QDAS_EINVAL, "migration: null descriptor");
+    if (d->flag != 0 && d->flag != 1 && d->flag != 2 && d->flag != 3 && d->flag != 5) return fail(QDAS_EINVAL, "migration: unknown interpolator flag (0 nearest, 1 linear, 2 cubic, 3 lanczos3, 5 cubic_dev)");
+    if ((d->keep_tx != 0 && d->keep_tx != 1) || (d->jacobian != 0 && d->jacobian != 1)) return fail(QDAS_EINVAL, "migration: keep_tx and jacobian are 0 or 1");
     const uint64_t LIM = 0x7fffff00ull;
-    if (d->T > LIM || d->N > LIM || d->M > LIM || d->frames > LIM || d->F > LIM || d->K > LIM) return mig_fail(QDAS_EUNSUPPORTED, "migration: every extent is at most 2^31 - 256");
+    if (d->T > LIM || d->N > LIM || d->M > LIM || d->frames > LIM || d->F > LIM || d->K > LIM) return fail(QDAS_EUNSUPPORTED, "migration: every extent is at most 2^31 - 256");
     if (d->T == 0 || d->N == 0 || d->M == 0 || d->frames == 0) return QDAS_OK;               // b has no elements: nothing is launched
-    if (d->F == 0 || d->K == 0) return mig_fail(QDAS_EINVAL, "migration: the transform lengths F and K are positive");
-    if (!finite_pos(d->fs) || !finite_pos(d->c0) || !finite_pos(d->pitch)) return mig_fail(QDAS_EINVAL, "migration: fs, c0 and pitch are positive and finite");
-    if (!(fabs(d->t0) < INFINITY) || !(fabs(d->fmod) < INFINITY)) return mig_fail(QDAS_EINVAL, "migration: t0 and fmod are finite");
+    if (d->F == 0 || d->K == 0) return fail(QDAS_EINVAL, "migration: the transform lengths F and K are positive");
+    if (!finite_pos(d->fs) || !finite_pos(d->c0) || !finite_pos(d->pitch)) return fail(QDAS_EINVAL, "migration: fs, c0 and pitch are positive and finite");
+    if (!(fabs(d->t0) < INFINITY) || !(fabs(d->fmod) < INFINITY)) return fail(QDAS_EINVAL, "migration: t0 and fmod are finite");
     Args a{};
     unsigned thF = 0, thK = 0;
     if (!fft_factor(d->F, a.stF, thF) || !fft_factor(d->K, a.stK, thK))
-        return mig_fail(QDAS_ENOTLDS, "migration: a transform length outside the in-LDS path (products of 2, 3, 5, 7, 11, 13 from 2 to 8192 whose stages fit a workgroup)");
+        return fail(QDAS_ENOTLDS, "migration: a transform length outside the in-LDS path (products of 2, 3, 5, 7, 11, 13 from 2 to 8192 whose stages fit a workgroup)");
     const uint32_t F = (uint32_t)d->F, K = (uint32_t)d->K;
     const uint32_t RS = (K + K / 16 + 1) | 1u;
     const size_t ldsK = sizeof(float2) * 2 * TF * RS, ldsF = sizeof(float2) * (F + F / 16 + 1), ldsC = 2 * ldsF;
-    if (ldsK > LAT_LDS_MAX) return mig_fail(QDAS_ENOTLDS, "migration: K outside the in-LDS path (two tiles of 16 x K points exceed the 160 KiB of LDS)");
-    if (!x || !b || !d->tau || !d->gamma) return mig_fail(QDAS_EINVAL, "migration: null data pointer");
-    MigDeviceGuard guard;
-    if (!guard.set(d->device)) return mig_fail(QDAS_EHIP, "hipSetDevice failed");
+    if (ldsK > LAT_LDS_MAX) return fail(QDAS_ENOTLDS, "migration: K outside the in-LDS path (two tiles of 16 x K points exceed the 160 KiB of LDS)");
+    if (!x || !b || !d->tau || !d->gamma) return fail(QDAS_EINVAL, "migration: null data pointer");
+    DeviceGuard guard(d->device);
+    if (guard.err != hipSuccess) return fail(QDAS_EHIP, "hipSetDevice failed");
     const hipStream_t s = (hipStream_t)stream;
 
     const uint32_t M = (uint32_t)d->M, Fk = (uint32_t)std::min<uint64_t>(d->T, F), Nn = (uint32_t)std::min<uint64_t>(d->N, K);
@@ -389,8 +382,8 @@ extern "C" int qdas_migration(const qdas_migration_desc *d, const void *x, void 
     float2 *tw = (float2 *)scratch.get(sizeof(float2) * ((size_t)F + K));
     float2 *W = (float2 *)scratch.get(per * Mb);
     float2 *P = (float2 *)scratch.get(slice * sizeof(float2) * (d->keep_tx ? Mb : nslice));
-    if (!tw || !W || !P) return mig_fail(QDAS_ENOMEM, "migration: no memory for the work space");
-    auto hip_fail = [&](hipError_t e) { (void)hipStreamSynchronize(s); return mig_fail(QDAS_EHIP, hipGetErrorString(e)); };
+    if (!tw || !W || !P) return fail(QDAS_ENOMEM, "migration: no memory for the work space");
+    auto hip_fail = [&](hipError_t e) { (void)hipStreamSynchronize(s); return fail(QDAS_EHIP, "%s", hipGetErrorString(e)); };
 
     const bool big = (thF >> 16) != 0;
     const unsigned nthF = thF & 0xffffu;

@@ -24,7 +24,7 @@
 #include <vector>
 #include "qdas_kernels.h"
 #include "fft_lds.h"
-extern "C" int qdas_internal_upload(void *dst, const void *src, size_t bytes);      // qdas_api.hip: host -> device through pinned staging
+#include "api_util.h"
 
 namespace qdas {
 
@@ -474,3 +474,42 @@ int fftconv_launch(const void *x, const void *taps, int taps_real, void *z, uint
 }
 
 }  // namespace qdas
+
+using namespace qdas;
+
+struct qdas_pre_plan { qdas::PrePlan *p; int device; };
+
+extern "C" int qdas_pre_plan_create(qdas_pre_plan **out, const qdas_pre_desc *d) {
+    if (!out || !d) return fail(QDAS_EINVAL, "null argument");
+    *out = nullptr;
+    if (d->in_type != QDAS_PRE_F32 && d->in_type != QDAS_PRE_I16) return fail(QDAS_EINVAL, "pre: input type must be fp32 or int16");
+    const uint64_t N = d->Nfft ? d->Nfft : d->T;
+    if (N >= (1ull << 31) || d->K >= (1ull << 31)) return fail(QDAS_EUNSUPPORTED, "pre: transform length / trace count too large");
+    if (d->fdown != 0.0 && !(d->fs > 0)) return fail(QDAS_EINVAL, "Undefined sampling rate.");
+    DeviceGuard guard(d->device);
+    HIPCHK(guard.err);
+    qdas_pre_plan *pl = new qdas_pre_plan();
+    { hipError_t e = hipGetDevice(&pl->device); if (e != hipSuccess) { delete pl; return fail(QDAS_EHIP, "hipGetDevice: %s", hipGetErrorString(e)); } }
+    const int rc = qdas::pre_create(&pl->p, d->T, d->K, d->Nfft, d->in_type, d->fs, d->t0, d->fdown);
+    if (rc) { delete pl; return fail(rc == 2 ? QDAS_ENOMEM : QDAS_EHIP, "pre: hipFFT plan / workspace creation failed"); }
+    *out = pl;
+    return QDAS_OK;
+}
+
+extern "C" int qdas_pre_execute(qdas_pre_plan *pl, const void *x, void *y, void *stream) {
+    if (!pl || !y) return fail(QDAS_EINVAL, "null argument");
+    DeviceGuard guard(pl->device);
+    HIPCHK(guard.err);
+    const int rc = qdas::pre_execute(pl->p, x, y, (hipStream_t)stream);
+    if (rc) return fail(QDAS_EHIP, "pre: hipFFT execution failed (%d)", rc);
+    return QDAS_OK;
+}
+
+extern "C" int qdas_pre_plan_one_pass(const qdas_pre_plan *pl) { return pl && qdas::pre_one_pass(pl->p) ? 1 : 0; }
+
+extern "C" void qdas_pre_plan_destroy(qdas_pre_plan *pl) {
+    if (!pl) return;
+    DeviceGuard guard(pl->device);
+    qdas::pre_destroy(pl->p);
+    delete pl;
+}

@@ -22,11 +22,9 @@
 #include <cstring>
 #include <string>
 #include <vector>
-extern "C" int qdas_internal_upload(void *dst, const void *src, size_t bytes);      // qdas_api.hip: host -> device through pinned staging
 
 #include "../../include/qdas.h"
-
-void qdas_internal_set_error(const char *msg);         // qdas_api.hip: the thread-local message behind qdas_last_error()
+#include "api_util.h"
 
 namespace {
 

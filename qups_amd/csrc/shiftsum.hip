@@ -18,6 +18,7 @@
 // Edge rule as everywhere (src/interpd.cu:70-150): a term counts iff all its taps lie in [0, T) and the position is >= 0.
 #include "qdas_device.h"
 #include "qdas_kernels.h"
+#include "api_util.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -396,3 +397,30 @@ hipError_t launch_shift_sum(const ShiftParams &P, int dtype, int cplx, int inter
 }
 
 }  // namespace qdas
+
+using namespace qdas;
+
+extern "C" int qdas_shift_sum(const qdas_shift_desc *d, const void *x, void *y, void *stream) {
+    if (!d || !y) return fail(QDAS_EINVAL, "null argument");
+    if (d->dtype != QDAS_F64 && d->dtype != QDAS_F32) return fail(QDAS_EUNSUPPORTED, "shift_sum: datatype must be double or single");
+    if ((d->flag & 7) > 5 || (d->flag & ~7)) return fail(QDAS_EINVAL, "Interp option not recognized: %d", d->flag);
+    if (!d->cplx && d->w && !d->w_real) return fail(QDAS_EINVAL, "shift_sum: real data take real weights");
+    if (d->To == 0 || d->N == 0 || d->Mo == 0 || d->F == 0) return QDAS_OK;
+    if (!d->shift || (!x && d->T > (uint64_t)(d->tpad > 0 ? d->tpad : 0) && d->M)) return fail(QDAS_EINVAL, "null data / shift pointer");
+    if (d->T >= (1ull << 31) || d->To >= (1ull << 31)) return fail(QDAS_EUNSUPPORTED, "shift_sum: at most 2^31 - 1 samples per trace");
+    if (d->N > 65535 || ((d->Mo + 7) / 8) * d->F > 65535) return fail(QDAS_EUNSUPPORTED, "shift_sum: too many receivers / synthesised transmits x frames for one launch");
+    if (d->M * d->Mo >= (1ull << 31)) return fail(QDAS_EUNSUPPORTED, "shift_sum: too many (element, transmit) pairs");
+    DeviceGuard guard(d->device);
+    HIPCHK(guard.err);
+    ShiftParams p{};
+    if (d->tpad < 0 || (uint64_t)d->tpad > d->T) return fail(QDAS_EINVAL, "shift_sum: tpad must lie in [0, T]");
+    p.x = x; p.y = y; p.T = d->T; p.To = d->To; p.N = d->N; p.M = d->M; p.Mo = d->Mo; p.F = d->F;
+    p.Tx = d->T - (uint64_t)d->tpad;
+    if (d->M == 0) {                                   // an empty sum
+        const size_t bytes = (size_t)d->To * d->N * d->Mo * d->F * (d->dtype == QDAS_F64 ? 8 : 4) * (d->cplx ? 2 : 1);
+        HIPCHK(hipMemsetAsync(y, 0, bytes, (hipStream_t)stream));
+        return QDAS_OK;
+    }
+    HIPCHK(launch_shift_sum(p, d->dtype, d->cplx ? 1 : 0, d->flag & 7, d->shift, d->w, d->w_real, (hipStream_t)stream));
+    return QDAS_OK;
+}

@@ -14,7 +14,9 @@
 // sums treat like MATLAB's sum(..., 'omitnan') when it is NaN (kern/wsinterpd.m:262).
 #include "qdas_device.h"
 #include "qdas_kernels.h"
+#include "api_util.h"
 #include <type_traits>
+#include <utility>
 #include <stdlib.h>
 
 namespace qdas {
@@ -358,7 +360,7 @@ __global__ void __launch_bounds__(256) wsinterpd_lanesum_kernel(const WsParams P
 }
 
 template <typename TY> static hipError_t launch_ws_t(const WsParams &P, hipStream_t s) {
-    if (P.stream_ok) {                                    // the lean streaming kernel (conditions checked by the host: qdas_api.hip)
+    if (P.stream_ok) {                                    // the lean streaming kernel (conditions checked by the host: qdas_wsinterpd below)
         constexpr int RUN = 8;
         const uint64_t nr = P.n_rest / P.size[0] * ((P.size[0] + RUN - 1) / RUN);       // dimension 0 in chunks of RUN
         const uint64_t gy = nr < 65535 ? (nr ? nr : 1) : 65535, gz = (nr + gy - 1) / gy;
@@ -439,3 +441,100 @@ hipError_t launch_wsinterpd(const WsParams &P, int dtype, hipStream_t s) {
 }
 
 }  // namespace qdas
+
+using namespace qdas;
+
+extern "C" int qdas_wsinterpd(const qdas_wsinterpd_desc *d, void *y, void *stream) {
+    if (!d || !y) return fail(QDAS_EINVAL, "null argument");
+    if (d->dtype < QDAS_F64 || d->dtype > QDAS_F16) return fail(QDAS_EINVAL, "Unrecognized input precision %d", d->dtype);
+    if ((d->flag & 7) > 5 || (d->flag & ~7)) return fail(QDAS_EINVAL, "Interp option not recognized: %d", d->flag);
+    if (d->ndim < 1 || d->ndim > 8) return fail(QDAS_EINVAL, "wsinterpd: 1..8 dimensions");
+    if (d->xstride[0] != 0) return fail(QDAS_EINVAL, "wsinterpd: xstride[0] must be 0 (dimension 0 is the sampling dimension)");
+    WsParams p{};
+    p.t = d->t; p.w = d->w; p.x = d->x; p.y = y;
+    p.T = d->T; p.x_tstride = d->x_tstride ? d->x_tstride : 1; p.nd = d->ndim;
+    p.n_out = 1; p.n_sum = 1;
+    for (int k = 0; k < d->ndim; ++k) {
+        p.size[k] = d->size[k]; p.tst[k] = d->tstride[k]; p.xst[k] = d->xstride[k]; p.wst[k] = d->wstride[k]; p.sum[k] = d->sum[k] ? 1 : 0;
+        if (p.sum[k]) { p.n_sum *= d->size[k]; p.any_sum = 1; } else p.n_out *= d->size[k];
+    }
+    p.omega = d->omega; p.extrap = d->extrap; p.flag = d->flag; p.w_real = d->w_real;
+    for (int k = 0; k < d->ndim; ++k) {                  // the summed dimensions, compacted (size-1 dimensions do not advance anything)
+        if (!p.sum[k] || d->size[k] <= 1) continue;
+        if (d->size[k] > 0xffffffffull) return fail(QDAS_EUNSUPPORTED, "wsinterpd: a summed dimension of more than 2^32 - 1 elements");
+        p.ssz[p.nsd] = (uint32_t)d->size[k]; p.sts[p.nsd] = d->tstride[k]; p.sxs[p.nsd] = d->xstride[k]; p.sws[p.nsd] = d->wstride[k];
+        ++p.nsd;
+    }
+    // kept dimensions in decode order: lane_dim first (default: the first kept dimension with more than one element), then the others ascending;
+    // y dense column-major over the kept dimensions unless the caller gave strides
+    {
+        bool ygiven = false;
+        for (int k = 0; k < d->ndim; ++k) if (d->ystride[k] != 0) ygiven = true;
+        int64_t acc = 1;
+        for (int k = 0; k < d->ndim; ++k) {
+            if (p.sum[k]) { p.yst[k] = 0; continue; }
+            p.yst[k] = ygiven ? d->ystride[k] : acc;
+            acc *= (int64_t)d->size[k];
+        }
+        int lane = d->lane_dim;
+        if (lane < 0 || lane >= d->ndim || p.sum[lane] || d->size[lane] <= 1) {
+            lane = -1;
+            for (int k = 0; k < d->ndim && lane < 0; ++k) if (!p.sum[k] && d->size[k] > 1) lane = k;
+            if (lane < 0) for (int k = 0; k < d->ndim && lane < 0; ++k) if (!p.sum[k]) lane = k;
+        }
+        if (lane < 0) { lane = 0; }                     // (every dimension summed: one output; dimension 0 then has size 1 in the output)
+        p.nkd = 0; p.n_rest = 1;
+        if (!p.sum[lane]) p.kord[p.nkd++] = lane;
+        // (the others by ascending memory stride of x -- dimension 0: the sample stride; where x broadcasts: of t --, so that a second lane dimension and
+        //  consecutive workgroups stay close in memory)
+        auto skey = [&](int k) -> uint64_t {
+            const uint64_t xs = k == 0 ? p.x_tstride : (uint64_t)(d->xstride[k] < 0 ? -d->xstride[k] : d->xstride[k]);
+            if (xs && (k == 0 || d->size[k] > 1)) return xs;
+            const uint64_t ts = (uint64_t)(d->tstride[k] < 0 ? -d->tstride[k] : d->tstride[k]);
+            return (1ull << 62) + (ts ? ts : (1ull << 61) + (uint64_t)k);
+        };
+        for (int k = 0; k < d->ndim; ++k) if (!p.sum[k] && k != lane) { p.kord[p.nkd++] = k; p.n_rest *= d->size[k]; }
+        for (int a = 1; a < p.nkd; ++a)                 // (insertion sort of at most 7 entries)
+            for (int b = a; b > 1 && skey(p.kord[b]) < skey(p.kord[b - 1]); --b) std::swap(p.kord[b], p.kord[b - 1]);
+        if (p.nkd == 0) {                               // all summed: a single output -- decode nothing (a pseudo dimension of size 1)
+            p.kord[0] = 0; p.nkd = 1;
+            static_assert(sizeof(p.size) / sizeof(p.size[0]) == 8, "");
+            // dimension 0 is summed here: give the lane loop a size-1 view of it through a spare slot
+            if (d->ndim < 8) { p.size[d->ndim] = 1; p.tst[d->ndim] = p.xst[d->ndim] = p.wst[d->ndim] = 0; p.yst[d->ndim] = 0; p.kord[0] = d->ndim; }
+            else return fail(QDAS_EUNSUPPORTED, "wsinterpd: all 8 dimensions summed");
+        }
+        p.n_lane = p.size[p.kord[0]];
+        p.lane2 = 0;
+        if (p.nkd >= 2 && (p.n_lane < 2048 || p.n_lane % 256 != 0) && p.n_lane * p.size[p.kord[1]] < (1ull << 31)) {   // a short (or ragged) fastest dimension: the lanes also cover the next one -- full workgroups
+            p.lane2 = 1;
+            p.n_lane *= p.size[p.kord[1]];
+            p.n_rest /= p.size[p.kord[1]] ? p.size[p.kord[1]] : 1;
+        }
+    }
+    {   // the lean streaming kernel (wsinterpd.hip interpd_stream_kernel): plain sampling, dimension 0 among the block-level dimensions, 32-bit extents
+        bool ok = !p.any_sum && !d->w && d->omega == 0.0 && p.nkd >= 2 && !getenv("QDAS_WS_GENERAL");
+        const int nl = p.lane2 ? 2 : 1;
+        for (int k = 0; k < nl && ok; ++k) if (p.kord[k] == 0) ok = false;
+        if (ok && p.nkd <= nl) ok = false;
+        auto ext = [&](const int64_t *st) { uint64_t e = 0; for (int k = 0; k < d->ndim; ++k) if (d->size[k] > 1) e += (uint64_t)(st[k] < 0 ? -st[k] : st[k]) * (d->size[k] - 1); return e; };
+        if (ok) {
+            for (int k = 0; k < d->ndim; ++k) if (p.tst[k] < 0 || p.xst[k] < 0 || p.yst[k] < 0) ok = false;
+            const uint64_t ex = ext(p.xst) + (uint64_t)p.x_tstride * (d->T ? d->T - 1 : 0);
+            if (ext(p.tst) >= (1ull << 31) || ex >= (1ull << 31) || ext(p.yst) >= (1ull << 31) || d->size[0] >= (1ull << 31) || d->T >= (1ull << 24)) ok = false;
+        }
+        p.stream_ok = ok ? 1 : 0;
+    }
+    // one summed dimension along which x is contiguous (a record in torch order -- last dimension fastest -- summed over that dimension): the lanes of a
+    // wave take the terms of ONE output and add up across the wave (wsinterpd.hip wsinterpd_lanesum_kernel) instead of one output per lane, every tap a
+    // 64-lane gather with one lane per memory row
+    p.lanesum_ok = (p.nsd == 1 && p.sxs[0] == 1 && p.ssz[0] >= 16 && p.ssz[0] < (1u << 31) && d->T > 1 && p.x_tstride > 1 && p.n_out < (1ull << 32) && !getenv("QDAS_WS_NO_LANESUM")) ? 1 : 0;
+    if (p.n_out == 0) return QDAS_OK;
+    if (p.n_out >= (1ull << 39)) return fail(QDAS_EUNSUPPORTED, "wsinterpd: too many outputs for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    if (p.n_sum == 0 || d->T == 0) {                     // empty sums / empty record
+        if (p.n_sum == 0 || p.any_sum || d->extrap == 0.0) { HIPCHK(hipMemsetAsync(y, 0, p.n_out * data_size(d->dtype), s)); return QDAS_OK; }
+    }
+    if (!d->t || (!d->x && d->T)) return fail(QDAS_EINVAL, "null data / delay pointer");
+    HIPCHK(launch_wsinterpd(p, d->dtype, s));
+    return QDAS_OK;
+}

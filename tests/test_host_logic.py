@@ -304,7 +304,7 @@ def test_bfDASLUT_error_identifiers_of_the_reference():
 
 @pytest.mark.gpu
 def test_staging_buffers_are_recycled_and_trimmed():
-    """qdas_device_malloc / free keep their buffers (a call-per-launch gateway maps nothing between calls: csrc/qdas_api.hip StagingCache): the same
+    """qdas_device_malloc / free keep their buffers (a call-per-launch gateway maps nothing between calls: csrc/staging.hip StagingCache): the same
     size class comes back with the same address, another class does not, uploads through qdas_device_copy land whole (odd sizes, unaligned tails),
     and qdas_device_trim releases the cache."""
     L = _lib.lib()
