@@ -1,52 +1,33 @@
-// das_tile.hip -- host side of the tiled kernel: launch configurations, LDS budget, dispatch to the per-configuration
-// translation units (das_tile_{f32,f32big,lut,luth,bf,sym,symw,symh,f16,f32x2,f16x2,f32x4,f16x4,f64}.hip, kernel in das_tile_impl.h) and the fixed-order
-// reduce of a split aperture.  -DQDAS_UNITY compiles everything as ONE translation unit (profiling / ablation builds that
-// pass -DQDAS_ABL / -DQDAS_PROF: tools/ablate.sh).
+// das_tile.hip -- host side of the tiled kernel: admission and choice of the launch configuration (plan_modes.h launch_legal), dispatch to the
+// per-configuration instantiations (das_tile_inst.hip, compiled once per row of das_tile_cfg.h CFGS that has a translation unit; kernel in
+// das_tile_impl.h) and the fixed-order reduce of a split aperture.  -DQDAS_UNITY compiles everything as ONE translation unit (profiling / ablation
+// builds that pass -DQDAS_ABL / -DQDAS_PROF: tools/ablate.sh).
 #ifdef QDAS_UNITY
-#include "das_tile_f32.hip"
-#include "das_tile_f16.hip"
-#include "das_tile_f32x2.hip"
-#include "das_tile_f16x2.hip"
-#include "das_tile_f32x4.hip"
-#include "das_tile_f16x4.hip"
-#include "das_tile_symh.hip"
-#include "das_tile_f32big.hip"
-#include "das_tile_lut.hip"
-#include "das_tile_luth.hip"
-#include "das_tile_bf.hip"
-#include "das_tile_f64.hip"
-#include "das_tile_f32w.hip"
-#include "das_tile_symqh.hip"
-#include "das_tile_fold.hip"
+#include "das_tile_inst.hip"
 #else
 #include "qdas_device.h"
 #include "das_tile_cfg.h"
 #endif
 #include "qdas_kernels.h"
 #include "jit.h"
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
 #include <set>
 #include <string>
+#include <utility>
 
 namespace qdas {
 
-hipError_t launch_tile_f32(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_f16(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_f32x2(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_f16x2(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_f32x4(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_f16x4(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_symh(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_f32big(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_lut(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_luth(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_bf(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_f64(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_f32w(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_symqh(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
-hipError_t launch_tile_fold(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
+// the instantiations of one launch configuration behind the interpolator switch (das_tile_inst.hip); nullptr: no translation unit
+using TileLauncher = hipError_t (*)(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
+#ifndef QDAS_UNITY
+template <int CI> hipError_t launch_tile_cfg(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s);
+#endif
+template <int CI> constexpr TileLauncher tile_launcher() { if constexpr (CFGS[CI].tu) return &launch_tile_cfg<CI>; else return nullptr; }
+template <int... CI> constexpr std::array<TileLauncher, sizeof...(CI)> tile_launchers(std::integer_sequence<int, CI...>) { return {tile_launcher<CI>()...}; }
+static constexpr auto LAUNCHERS = tile_launchers(std::make_integer_sequence<int, NCFG>{});      // indexed by the configuration number
 
 // y[i] = sum over the ksplit partial images, in split order (deterministic)
 // (fp64 data: complex128 partial images)
@@ -108,22 +89,16 @@ hipError_t launch_tile(const TileParams &P, int dtype, unsigned ntiles, hipStrea
     if (ntiles == 0) return hipSuccess;
     modes::LaunchChoice ch;
     if (modes::launch_legal(launch_shape(P, dtype, jit != nullptr), &ch)) return hipErrorInvalidValue;
-    const int sym = P.sym ? 1 : 0;
-    if (dtype == 0) {                                    // fp64 data: one frame, one workgroup per tile, plain 'DAS' sum, prebuilt kernels
-        const size_t lds64 = ch.lds;
-        hipError_t e64 = jit ? jit_launch(jit, P, ntiles * P.ksplit, (unsigned)CFGS[13].waves * 64u, lds64, s) : launch_tile_f64(P, ntiles, lds64, s);
-        if (e64 != hipSuccess || P.probe || P.ksplit <= 1 || g_prepare_only) return e64;
+    if (ch.cfg == CFG_NONE || (!jit && !LAUNCHERS[ch.cfg])) return hipErrorInvalidValue;
+    const bool f64 = dtype == 0;                         // fp64 data: one frame, one workgroup per tile, plain 'DAS' sum; its LDS image is launch_legal's, also for a hiprtc build
+    const hipError_t e = jit ? jit_launch(jit, P, ntiles * P.ksplit, (unsigned)CFGS[ch.cfg].waves * 64u, (jit_lds && !f64) ? jit_lds : ch.lds, s)
+                             : LAUNCHERS[ch.cfg](P, ntiles, ch.lds, s);
+    if (e != hipSuccess || P.probe || P.ksplit <= 1 || P.syn || P.bf || g_prepare_only) return e;   // ('SYN' planes are accumulated in place, 'BF' planes stored by their owners)
+    if (f64) {
         tile_reduce_kernel_f64<<<(unsigned)((P.i_count + 255) / 256), 256, 0, s>>>((const double2 *)P.part, (double2 *)P.y, P.i_count, P.ksplit);
         return hipGetLastError();
     }
-    const int narrow = ch.narrow, fold = ch.fold, mirq = ch.mirq, nfr = ch.nfr, nf = ch.nf;
-    const bool probe_f32sym = ch.probe_f32sym;
-    const size_t lds = ch.lds;
-    hipError_t e = jit ? jit_launch(jit, P, ntiles * P.ksplit, (unsigned)CFGS[cfg_index(dtype, sym, 1, narrow, mirq, fold)].waves * 64u, jit_lds ? jit_lds : lds, s) : (fold || probe_f32sym) ? launch_tile_fold(P, ntiles, lds, s) : P.lut_tx ? (dtype == 2 ? launch_tile_luth(P, ntiles, lds, s) : launch_tile_lut(P, ntiles, lds, s)) : (mirq && dtype == 2) ? launch_tile_symqh(P, ntiles, lds, s) : (sym && dtype == 2) ? launch_tile_symh(P, ntiles, lds, s) : sym ? hipErrorInvalidValue
-                 : nf == 4 ? (dtype == 2 ? launch_tile_f16x4(P, ntiles, lds, s) : launch_tile_f32x4(P, ntiles, lds, s))
-                 : nf == 2 ? (dtype == 2 ? launch_tile_f16x2(P, ntiles, lds, s) : launch_tile_f32x2(P, ntiles, lds, s))
-                           : (dtype == 2 ? launch_tile_f16(P, ntiles, lds, s) : narrow == 2 ? launch_tile_f32w(P, ntiles, lds, s) : (P.bf && !P.probe) ? launch_tile_bf(P, ntiles, lds, s) : (P.big && !P.probe) ? launch_tile_f32big(P, ntiles, lds, s) : launch_tile_f32(P, ntiles, lds, s));
-    if (e != hipSuccess || P.probe || P.ksplit <= 1 || P.syn || P.bf || g_prepare_only) return e;   // ('SYN' planes are accumulated in place, 'BF' planes stored by their owners)
+    const int nfr = ch.nfr;
     const uint64_t oc = P.mir == 2 ? 2 * P.i_count : P.i_count;     // pixels the plan writes (a mirror slab: slab A and its image)
     const unsigned rb = (unsigned)((oc + 255) / 256);
     for (int f = 0; f < nfr; ++f) {                      // partial images: [split][frame][pixel]

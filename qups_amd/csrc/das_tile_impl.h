@@ -952,9 +952,8 @@ bool tile_prepare_only();          // das_tile.hip: this thread is resolving a p
 template <int INTERP, typename ST, int CI>
 static hipError_t launch_tile_i(const TileParams &P, unsigned ntiles, size_t lds, hipStream_t s) {
     constexpr Cfg G = CFGS[CI];
-    constexpr bool FOLD = (CI >= 17 && CI <= 21);       // folded data: with the lateral-mirror mode (narrow / wide windows), without; 20 / 21: two frames per launch
-    constexpr bool MIRQ = (CI == 15 || CI == 16 || CI == 17 || CI == 18 || CI == 20);
-    constexpr bool SYM = (CI == 1 || CI == 7 || CI == 8 || MIRQ || FOLD), FB2 = (CI == 3 || CI == 4 || CI == 20 || CI == 21), FB4 = (CI == 5 || CI == 6), BIG = (CI == 9), LUT = (CI == 10 || CI == 11), BFM = (CI == 12);
+    static_assert((int)sizeof(ST) == G.bytes, "sample type of the configuration");
+    constexpr bool FOLD = G.fold, MIRQ = G.mirq, SYM = G.sym, FB2 = G.frames == 2, FB4 = G.frames == 4, BIG = G.big, LUT = G.lut, BFM = G.bfm;
     const bool fm = P.fmod != 0.0, wt = P.wtab != nullptr;
     const dim3 g(ntiles * (P.probe ? 1u : P.ksplit)), b(G.waves * 64);
     tile_census(CI, INTERP, (int)sizeof(ST), fm, wt, P.probe != 0);

@@ -15,7 +15,8 @@
 //                           what is given up when tiles do not fit (narrow windows -> wide, mirror mode -> plain)
 //   4. choose_ksplit        workgroups per tile
 //   5. stream_modes         frames per launch of a stream
-//   6. launch_legal         the launcher's own admission rules (das_tile.hip launch_tile calls THIS: one source of truth)
+//   6. launch_legal         the launcher's own admission rules AND the launch configuration it runs (das_tile.hip launch_tile calls THIS and dispatches on
+//                           LaunchChoice::cfg: one source of truth)
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -437,7 +438,7 @@ struct LaunchShape {
     uint32_t act_bytes = 0, ksplit = 1;
     uint64_t N = 0, M = 0;
 };
-struct LaunchChoice { int narrow = 0, fold = 0, mirq = 0, nf = 1, nfr = 1; bool probe_f32sym = false; size_t lds = 0; int cfg = 0; };
+struct LaunchChoice { int nfr = 1; size_t lds = 0; int cfg = 0; };      // nfr: frames of the launch; cfg: the configuration that is launched (das_tile_cfg.h select_cfg)
 
 inline const char *launch_legal(const LaunchShape &P, LaunchChoice *c) {
     const int dtype = P.dtype, sym = P.sym ? 1 : 0;
@@ -447,7 +448,7 @@ inline const char *launch_legal(const LaunchShape &P, LaunchChoice *c) {
         if (P.lut || P.bf || P.syn || P.big || P.nfr > 1 || (P.jit && P.probe) || (!P.probe && (P.ksplit < 1 || (P.ksplit > 1 && !P.has_part)))) return "fp64 data: plain 'DAS', one frame per launch";
         ch.lds = tile_lds_bytes(0, 0, P.N, P.M, 0);
         if (ch.lds > tile_lds_limit(0)) return "fp64 data: LDS image too large";
-        ch.cfg = 13;
+        ch.cfg = select_cfg(0, 0);
         if (c) *c = ch;
         return nullptr;
     }
@@ -477,8 +478,8 @@ inline const char *launch_legal(const LaunchShape &P, LaunchChoice *c) {
     if (P.lut && (sym || (nf != 1 && !(P.mir && P.jit && nf == 2 && dtype == 1 && !P.syn)) || (dtype != 1 && dtype != 2) || (P.syn && dtype != 1))) return "table-driven delays: general mode, one frame";
     if (P.jit && (P.probe || nfr != 1 || (P.lut && !P.mir) || P.bf)) return "hiprtc builds: one frame, no probe / 'BF'; table-driven delays in lateral-mirror mode only";
     if (P.bf && (sym || nf != 1 || dtype != 1 || P.lut || P.big || P.has_apix || P.gen_kind)) return "'BF': fp32 general mode without pixel weights";
-    ch.narrow = narrow; ch.fold = fold; ch.mirq = mirq; ch.nf = nf; ch.nfr = nfr; ch.probe_f32sym = probe_f32sym; ch.lds = lds;
-    ch.cfg = cfg_index(dtype, sym, 1, narrow, mirq, fold);
+    ch.nfr = nfr; ch.lds = lds;
+    ch.cfg = select_cfg(dtype, sym, nf, narrow, mirq, fold, P.big, P.lut, P.bf, P.probe);     // (CFG_NONE, or a row without a translation unit and no hiprtc build: the launcher refuses)
     if (c) *c = ch;
     return nullptr;
 }

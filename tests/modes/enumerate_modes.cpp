@@ -120,6 +120,7 @@ static void draw(uint64_t seed, Drawn &D) {
 }
 
 static long g_fail = 0;
+static bool named_cfg(int c) { return c >= 0 && c < NCFG; }
 #define EXPECT(c, ...) do { if (!(c)) { if (g_fail++ < 20) { printf("FAILED %s:%d  %s\n   ", __FILE__, __LINE__, #c); printf(__VA_ARGS__); printf("\n"); } } } while (0)
 
 int main(int argc, char **argv) {
@@ -186,8 +187,11 @@ int main(int argc, char **argv) {
                     L.dtype = dt; L.sym = s.sym; L.fold = s.rfold; L.mir = s.mir; L.narrow_raw = s.narrow; L.big = sy.big; L.bf = rq.bfm; L.syn = rq.syn; L.probe = 1;
                     L.N = sy.kN; L.M = sy.kM; L.has_bpix = false;
                     L.act_bytes = ((rq.pix_arr >= 0 || d.rx_apod_kind) && dt != QDAS_F64) ? (uint32_t)(8 * (sy.kN + 1)) : 0u;
-                    const char *why = launch_legal(L, nullptr);
+                    LaunchChoice pc;
+                    const char *why = launch_legal(L, &pc);
                     EXPECT(!why, "probe launch refused (%s): %s", why, D.text.c_str());
+                    // (das_tile_impl.h launch_tile_i refuses probes on the rows that share a launch between frames; probe kernels are all prebuilt)
+                    EXPECT(why || (named_cfg(pc.cfg) && CFGS[pc.cfg].tu && CFGS[pc.cfg].frames == 1), "probe launch on configuration %d: %s", pc.cfg, D.text.c_str());
                     const TileConfig tc = s.tc();
                     EXPECT(tc.mb > 0 && tc.window > 0, "%s", D.text.c_str());
                     *fit = nprobe < 3 ? ((po >> nprobe) & 1) != 0 : true;
@@ -229,8 +233,9 @@ int main(int argc, char **argv) {
                     EXPECT(!why, "one-frame launch refused (%s): %s [sym %d fold %d mir %d narrow %d big %d wide %d split %d ks %u]", why, D.text.c_str(), L.sym, L.fold, L.mir, L.narrow_raw, L.big,
                            (int)o.wide, (int)o.side_split, o.ksplit);
                     if (why) continue;
-                    EXPECT(ch.cfg >= 0 && ch.cfg < 22 && ch.lds <= tile_lds_limit(L.sym), "cfg %d lds %zu: %s", ch.cfg, ch.lds, D.text.c_str());
-                    ++cfgs[L.big ? 9 : L.bf ? 12 : ch.cfg];          // (cfg_index does not encode the re-basing / 'BF' instantiations)
+                    EXPECT(named_cfg(ch.cfg) && ch.lds <= tile_lds_limit(L.sym), "cfg %d lds %zu: %s", ch.cfg, ch.lds, D.text.c_str());
+                    EXPECT(!named_cfg(ch.cfg) || L.jit || CFGS[ch.cfg].tu, "one-frame launch on configuration %d, which has no translation unit: %s", ch.cfg, D.text.c_str());
+                    ++cfgs[ch.cfg];
                     // ---- streams: every frame-sharing launch stream_modes admits must be legal (prebuilt kernels: no hiprtc build shares frames)
                     PlanShape p;
                     p.dtype = dt; p.tiled = true; p.sym = L.sym; p.fold = L.fold; p.mir = L.mir; p.narrow = L.narrow_raw; p.big = L.big; p.bf = L.bf; p.syn = L.syn; p.stage_shift = L.stage_shift;
@@ -242,9 +247,11 @@ int main(int argc, char **argv) {
                         LaunchShape L2 = L;
                         L2.nfr = nf; L2.jit = false;
                         L2.has_part = o.ksplit > 1 && !L.bf;
-                        const char *w2 = launch_legal(L2, nullptr);
+                        LaunchChoice c2;
+                        const char *w2 = launch_legal(L2, &c2);
                         EXPECT(!w2, "%d-frame launch refused (%s): %s", nf, w2, D.text.c_str());
-                        if (!w2) ++cfgs[cfg_index(dt, L2.sym, nf, 0, L2.mir && L2.sym, L2.fold)];
+                        EXPECT(w2 || (named_cfg(c2.cfg) && CFGS[c2.cfg].tu && CFGS[c2.cfg].frames == nf), "%d-frame launch on configuration %d: %s", nf, c2.cfg, D.text.c_str());
+                        if (!w2) ++cfgs[c2.cfg];
                     }
                     ++resolved;
                 }
