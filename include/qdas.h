@@ -598,6 +598,44 @@ typedef struct qdas_migration_desc {
 } qdas_migration_desc;
 int qdas_migration(const qdas_migration_desc *desc, const void *x, void *b, void *stream);
 
+/* ---- Pair-wise windowed zero-normalized cross-correlation (pwznxcorr.hip): the base-MATLAB branch of the reference's kern/pwznxcorr.m (iflt = false:
+ * convn(., w, 'same'), a zero pad at the end of the record, circshift) for every lag in ONE launch.  With h = floor(W / 2), P = max|lags| when `pad` (else 0),
+ * Tp = T + P, both records extended by P zeros, K(a)[s] = sum_k w[k] a[s + h - k] for s in [0, Tp) and a = 0 outside [0, Tp) (MATLAB's 'same'):
+ *   xlz = xl - K(xl) when `zero`, else xl;                xln = K(|xlz|^2)
+ *   per lag l:  c[s] = conj(xr[(s + l) mod Tp]);          cz = c - K(c) when `zero`, else c
+ *   y_l = K(xlz cz),  with `norm` divided by sqrt(xln) sqrt(K(|cz|^2)) (0 / 0 stays NaN);     the result is y_l[0 .. T-1].
+ * `zero` subtracts the weighted window SUM as the reference does (weights ones(W) / W give the usual ZNCC); in the pad region xlz is -K(xl), not 0, and
+ * for a positive lag the first l samples wrap into the pad region: both are reproduced.
+ * xl, xr: DEVICE arrays of `dtype` (QDAS_F64 | QDAS_F32), real or interleaved complex, of N channel pairs x bsize[0] x bsize[1] records of T samples, the
+ * samples of a record contiguous (stride 1); the other strides count elements (complex samples when cplx) and are given per operand -- xr may be xl
+ * shifted by a channel stride (neighbouring channels) or broadcast one record with a stride of 0.  w: DEVICE array of W real `dtype` weights; with `norm`
+ * they must not be negative (the reference's denominator turns complex; the caller checks).  lags: HOST table of nlags integers, in any order, duplicates
+ * allowed, read during the call only.  y: DEVICE array of `dtype` (complex when cplx): y[t + n y_strideN + b0 y_bstride[0] + b1 y_bstride[1] + i y_strideL]
+ * for lag i.  Every sum is a direct weighted sum over the window in the data's precision; no atomics: results are bit-reproducible.
+ * A workgroup owns QDAS_PWZNXCORR_TIME_TILE output times of one record pair and keeps tile + 2 (W - 1) samples of the left and tile + 2 (W - 1) + (max lag -
+ * min lag) samples of the right record in LDS (qdas_pwznxcorr_lds_bytes); beyond 64 KiB -- W = 256 with lags -256 .. 256 in complex double needs 53144
+ * bytes and is inside --, more than QDAS_PWZNXCORR_MAX_LAGS lags, a lag beyond +-32767 or more than 2^31 - 1 workgroups: QDAS_EUNSUPPORTED, nothing is
+ * launched.  The arguments are validated before any HIP call; T, N, a batch size or nlags = 0 is an empty result: nothing is launched, the data pointers may be NULL. */
+#define QDAS_PWZNXCORR_TIME_TILE 256
+#define QDAS_PWZNXCORR_MAX_LAGS  1024
+typedef struct qdas_pwznxcorr_desc {
+    int32_t  dtype;               /* QDAS_F64 | QDAS_F32                              */
+    int32_t  cplx;                /* samples are interleaved complex                  */
+    int32_t  device;              /* HIP device ordinal, -1 = current                 */
+    int32_t  zero, norm, pad;     /* 0 | 1: the reference's options of the same names */
+    uint64_t T;                   /* samples per record                               */
+    uint64_t N;                   /* channel pairs                                    */
+    uint64_t W;                   /* window length (>= 1)                             */
+    uint64_t nlags;
+    uint64_t bsize[2];            /* batch groups; unused: 1 (stride 0)               */
+    int64_t  xl_strideN, xl_bstride[2];
+    int64_t  xr_strideN, xr_bstride[2];
+    int64_t  y_strideN, y_bstride[2], y_strideL;
+} qdas_pwznxcorr_desc;
+int qdas_pwznxcorr(const qdas_pwznxcorr_desc *desc, const void *xl, const void *xr, const void *w, const int64_t *lags, void *y, void *stream);
+int qdas_pwznxcorr_time_tile(void);                                                   /* QDAS_PWZNXCORR_TIME_TILE of the library as built */
+uint64_t qdas_pwznxcorr_lds_bytes(int dtype, int cplx, uint64_t W, uint64_t span);    /* LDS of one workgroup; span = max lag - min lag */
+
 /* ---- Temporaries of the stream entries (qdas_shift_sum, qdas_das_lut, qdas_greens, qdas_convd's FFT path): taken from an arena the library keeps per (device,
  * stream).  One such call at a time runs per (device, stream) -- a second thread on the same stream waits --, and a call MAY BLOCK the host: when the stream's
  * previous call outgrew the arena (the next call waits for it, then regrows the arena to what that call needed, up to 512 MiB) or asks for a single temporary above

@@ -43,6 +43,12 @@
  *         ksz = [A N B K C kfirst]: x is A x N x B x K x C column-major (as kern/slsc.m's OpenCL branch sizes it: A = prod(sz(1:dim-1)), N = sz(dim),
  *         ...), N the reduced aperture, K a second reduced dimension (slsc's kdim, cohfac's second dim; omitted = 1), kfirst = 1: x is A x K x B x N x C
  *         (kdim < dim).  The result is A x B x C (the caller reshapes it to size(x) with the reduced dimensions set to 1); complex for complex slsc / dmas.
+ * Pair-wise windowed zero-normalized cross-correlation (kern/pwznxcorr.m, the base-MATLAB branch: iflt = false), every lag in one launch:
+ *   y       = qdas_mex('pwznxcorr', psz, xl, xr, w, lags)
+ *         psz = [T N B zero norm pad rN rB]: xl is T x N x B column-major (real or complex single / double), the left traces; xr the right traces of the same
+ *         class and complexity, T x (rN ? N : 1) x (rB ? B : 1) (rN / rB = 0: one trace for every channel / batch entry; omitted = 1); w: the real window
+ *         weights of x's class (the caller expands a scalar W to ones(W, 1)); lags: integers, any order.  y is T x N x B x numel(lags), complex for complex x.
+ *         The caller slices x into xl / xr as the reference does (sub(x, 1:N-S, ndim) / sub(x, 1+S:N, ndim), the centre trace, x0).
  * Travel times through a speed map (kern/msfm.m with two arguments: first order, four neighbours; what bfEikonal's parfor loops compute one element at a time):
  *   T       = qdas_mex('msfm', csz, F, src, first, max_passes)
  *         csz = [C1 C2]; F: C1 x C2 double, host or gpuArray, the speed in cells per second; src: 2 x P double (host), 1-based points, floored to a node;
@@ -627,6 +633,56 @@ static void cmd_coherence(const char *cmd, int nlhs, mxArray *plhs[], int nrhs, 
     if (host2) plhs[1] = host2;
 }
 
+/* y = qdas_mex('pwznxcorr', psz, xl, xr, w, lags) -- kern/pwznxcorr.m:241-299 (iflt = false, integer lags, U = 1, multi = false) */
+static mxArray *cmd_pwznxcorr(int nrhs, const mxArray *prhs[]) {
+    if (nrhs != 5) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('pwznxcorr', psz, xl, xr, w, lags)");
+    qdas_pwznxcorr_desc d;
+    memset(&d, 0, sizeof d);
+    const mxArray *p = prhs[0], *xl = prhs[1], *xr = prhs[2], *wa = prhs[3], *la = prhs[4];
+    const size_t np = mxGetNumberOfElements(p);
+    const uint64_t T = (uint64_t)num_at(p, 0, "psz"), N = (uint64_t)num_at(p, 1, "psz"), B = (uint64_t)num_at(p, 2, "psz");
+    d.zero = num_at(p, 3, "psz") != 0; d.norm = num_at(p, 4, "psz") != 0; d.pad = num_at(p, 5, "psz") != 0;
+    const int rN = np > 6 ? num_at(p, 6, "psz") != 0 : 1, rB = np > 7 ? num_at(p, 7, "psz") != 0 : 1;
+    const mxClassID cls = mxGetClassID(xl);
+    if (cls != mxDOUBLE_CLASS && cls != mxSINGLE_CLASS) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "pwznxcorr: x must be single or double.");
+    if (mxGetClassID(xr) != cls || mxIsComplex(xr) != mxIsComplex(xl)) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "pwznxcorr: xl and xr must have the same class and complexity.");
+    if (mxGetClassID(wa) != cls || mxIsComplex(wa)) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "pwznxcorr: the weights must be real and of x's class.");
+    d.dtype = cls == mxDOUBLE_CLASS ? QDAS_F64 : QDAS_F32;
+    d.cplx = mxIsComplex(xl) ? 1 : 0;
+    d.device = -1;
+    d.T = T; d.N = N; d.W = (uint64_t)mxGetNumberOfElements(wa); d.nlags = (uint64_t)mxGetNumberOfElements(la);
+    d.bsize[0] = B; d.bsize[1] = 1;
+    const uint64_t xrN = rN ? N : 1;
+    d.xl_strideN = (int64_t)T; d.xl_bstride[0] = (int64_t)(T * N);
+    d.xr_strideN = rN ? (int64_t)T : 0; d.xr_bstride[0] = rB ? (int64_t)(T * xrN) : 0;
+    d.y_strideN = (int64_t)T; d.y_bstride[0] = (int64_t)(T * N); d.y_strideL = (int64_t)(T * N * B);
+    if (d.W == 0) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "pwznxcorr: the window is empty.");
+    for (uint64_t i = 0; i < d.nlags; ++i) {                           /* (raises here for complex, non-numeric or non-integer lags, before anything is staged) */
+        const double l = num_at(la, (mwSize)i, "lags");
+        if ((double)(int64_t)l != l) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "pwznxcorr: lags must be integers.");
+    }
+#ifdef QDAS_MEX_GPU
+    if (!mxIsGPUArray(wa))
+#endif
+    if (d.norm) for (uint64_t k = 0; k < d.W; ++k) if (num_at(wa, (mwSize)k, "w") < 0) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "pwznxcorr: a negative weight needs norm = false.");
+    const size_t es = d.dtype == QDAS_F64 ? 8 : 4, xs = es * (d.cplx ? 2 : 1);
+    const mwSize dims[4] = {(mwSize)T, (mwSize)N, (mwSize)B, (mwSize)d.nlags};
+    if (T * N * B * d.nlags == 0) return mxCreateNumericArray(4, dims, cls, d.cplx ? mxCOMPLEX : mxREAL);   /* an empty result: nothing staged or launched */
+    int dev = 0;
+    const void *pl = dev_in(xl, (size_t)(T * N * B) * xs, "xl", &dev);
+    const void *pr = dev_in(xr, (size_t)(T * xrN * (rB ? B : 1)) * xs, "xr", &dev);
+    const void *pw = dev_in(wa, (size_t)d.W * es, "w", &dev);
+    const size_t bytes = (size_t)(T * N * B * d.nlags) * xs;
+    mxArray *host;
+    void *y = dev_out(4, dims, cls, d.cplx, dev, bytes, &host);
+    int64_t *tab = (int64_t *)malloc(sizeof(int64_t) * d.nlags);
+    if (!tab) { if (host) mxDestroyArray(host); CFAIL("out of host memory."); }
+    for (uint64_t i = 0; i < d.nlags; ++i) tab[i] = (int64_t)num_at(la, (mwSize)i, "lags");
+    const int rc = qdas_pwznxcorr(&d, pl, pr, pw, tab, y, NULL);
+    free(tab);
+    return finish(rc, host, bytes);
+}
+
 /* T = qdas_mex('msfm', csz, F, src, first, max_passes) -- kern/msfm.m:93-113 (UseSecond = UseCross = false), one call for every source set */
 static mxArray *cmd_msfm(int nrhs, const mxArray *prhs[]) {
     if (nrhs < 3 || nrhs > 5) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('msfm', csz, F, src, first, max_passes)");
@@ -783,6 +839,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "convd")) { plhs[0] = cmd_convd(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "hilbert")) { plhs[0] = cmd_hilbert(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "slsc") || !strcmp(cmd, "dmas") || !strcmp(cmd, "cohfac") || !strcmp(cmd, "pcf")) { cmd_coherence(cmd, nlhs, plhs, nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "pwznxcorr")) { plhs[0] = cmd_pwznxcorr(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "msfm")) { plhs[0] = cmd_msfm(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "adjoint")) { plhs[0] = cmd_adjoint(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "migration")) { plhs[0] = cmd_migration(nrhs - 1, prhs + 1);

@@ -27,6 +27,7 @@ PLAN_NO_RECIPROCAL, PLAN_JIT, PLAN_COPY_INPUTS, PLAN_NO_MIRROR, PLAN_MIRROR_SLAB
 COH_SLSC_AVERAGE, COH_SLSC_ENSEMBLE, COH_DMAS, COH_COHFAC, COH_PCF = 1, 2, 3, 4, 5
 QDAS_ENOCONV = 5
 QDAS_ENOTLDS = 6
+QDAS_EUNSUPPORTED = 2
 RXAPOD_NONE, RXAPOD_ACCEPTANCE, RXAPOD_COSINE, RXAPOD_FNUMBER_PLANAR, RXAPOD_FNUMBER_ORIENTED = 0, 1, 2, 3, 4
 
 # every symbol include/qdas.h declares (tests check the library exports all of them)
@@ -37,6 +38,7 @@ SYMBOLS = (
     "qdas_plan_destroy_sharded", "qdas_DAS", "qdas_DASf", "qdas_DASh", "qdas_delays", "qdas_delaysf",
     "qdas_das_lut", "qdas_das_lut_last_kernel", "qdas_wsinterpd", "qdas_shift_sum", "qdas_greens", "qdas_convd", "qdas_convd_len", "qdas_permute3", "qdas_pre_plan_create", "qdas_pre_execute", "qdas_pre_plan_destroy", "qdas_pre_plan_one_pass", "qdas_last_error", "qdas_version", "qdas_device_malloc", "qdas_device_free", "qdas_device_trim", "qdas_device_copy", "qdas_iir", "qdas_device_info", "qdas_kernel_variant_build", "qdas_kernel_variant_prebuilt",
     "qdas_coherence", "qdas_eikonal", "qdas_eikonal_tables", "qdas_eikonal_last_passes", "qdas_eikonal_pass_cap", "qdas_adjoint", "qdas_migration",
+    "qdas_pwznxcorr", "qdas_pwznxcorr_time_tile", "qdas_pwznxcorr_lds_bytes",
 )
 
 
@@ -130,6 +132,13 @@ class MigrationDesc(C.Structure):
                 ("tau", C.c_void_p), ("gamma", C.c_void_p)]
 
 
+class PwznxcorrDesc(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("cplx", C.c_int32), ("device", C.c_int32), ("zero", C.c_int32), ("norm", C.c_int32), ("pad", C.c_int32),
+                ("T", C.c_uint64), ("N", C.c_uint64), ("W", C.c_uint64), ("nlags", C.c_uint64), ("bsize", C.c_uint64 * 2),
+                ("xl_strideN", C.c_int64), ("xl_bstride", C.c_int64 * 2), ("xr_strideN", C.c_int64), ("xr_bstride", C.c_int64 * 2),
+                ("y_strideN", C.c_int64), ("y_bstride", C.c_int64 * 2), ("y_strideL", C.c_int64)]
+
+
 class QdasError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libqdas error {code}: {msg}")
@@ -195,6 +204,10 @@ def lib():
     L.qdas_eikonal_pass_cap.restype = C.c_uint32
     L.qdas_adjoint.argtypes = [C.POINTER(AdjointDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_migration.argtypes = [C.POINTER(MigrationDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qdas_pwznxcorr.argtypes = [C.POINTER(PwznxcorrDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
+    L.qdas_pwznxcorr_time_tile.argtypes = []
+    L.qdas_pwznxcorr_lds_bytes.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64]
+    L.qdas_pwznxcorr_lds_bytes.restype = C.c_uint64
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64
     L.qdas_shift_sum.argtypes = [C.POINTER(ShiftDesc), C.c_void_p, C.c_void_p, C.c_void_p]
