@@ -200,7 +200,8 @@ typedef struct qdas_plan qdas_plan; /* opaque: device copies of geometry + strid
 int  qdas_plan_create(qdas_plan **plan, const qdas_desc *desc);
 /* Beamform ONE frame: x is T x N x M (or T x M x N with QDAS_FLAG_TPOSE) complex(prec);
  * y is i_count x [1|N] x [1|M] complex(prec) with plane stride y_ld; y is fully
- * overwritten.  Asynchronous on `stream` when desc.mem == QDAS_MEM_DEVICE. */
+ * overwritten.  Asynchronous on `stream` when desc.mem == QDAS_MEM_DEVICE.  A plan owns device scratch (fold buffer, misfit-tile list, partial images):
+ * two streams may use one plan only one after the other, with an event (or a synchronisation) between the calls; concurrent use is not supported. */
 int  qdas_plan_execute(qdas_plan *plan, const void *x, void *y, void *stream);
 /* F frames in one call (kern/das_spec.m:371-373 host loop): frame f uses
  * x + f*x_stride and y + f*y_stride (strides in complex elements).  Device-resident frames of a tiled plan share launches
@@ -285,7 +286,8 @@ void qdas_plan_destroy_sharded(qdas_sharded_plan *plan);
 
 /* ---- one-shot entries shaped like the reference kernels' argument lists
  *      (device pointers; sizes struct replaces the constant-memory symbols).
- *      DAS  <-> src/bf.cu:144-151, DASf <-> :153-161, DASh <-> :164-171 */
+ *      DAS  <-> src/bf.cu:144-151, DASf <-> :153-161, DASh <-> :164-171.  The arrays may still be in the making on `stream`: the call waits for `stream`
+ *      before it reads the geometry (a plan is created, executed and destroyed inside the call) and again before it returns. */
 int qdas_DAS (const qdas_sizes *sz, void *y, const double *Pi, const double *Pr, const double *Pv,
               const double *Nv, const void *a, const double *cinv, const uint64_t *acstride_host,
               const void *x, const double tvars[2], void *stream);

@@ -1563,6 +1563,9 @@ static int one_shot(const qdas_sizes *sz, int dtype, void *y, const void *Pi, co
     d.fs = fs; d.fmod = fmod;
     d.Pi = Pi; d.Pr = Pr; d.Pv = Pv; d.Nv = Nv; d.apod = a; d.cinv = cinv; d.acstride = acs;
     d.mem = QDAS_MEM_DEVICE; d.device = -1; d.kernel = QDAS_KERNEL_AUTO;
+    // qdas_plan_create reads the geometry, the weights and cinv on the NULL stream, which is not ordered with a non-blocking `stream`: whatever the caller queued
+    // there to produce them has to be done first (the call waits for `stream` at its end anyway)
+    if (stream) { hipError_t e = hipStreamSynchronize((hipStream_t)stream); if (e != hipSuccess) return fail(QDAS_EHIP, "sync: %s", hipGetErrorString(e)); }
     qdas_plan *pl = nullptr;
     int rc = qdas_plan_create(&pl, &d);
     if (rc) return rc;

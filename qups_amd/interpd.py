@@ -135,6 +135,8 @@ def _shift_tables(shift, w, M, dbl, cplx_data, dev, torch):
     if host:
         import collections, hashlib
         sa = np.ascontiguousarray(np.asarray(shift, np.float64))
+        if sa.ndim != 2 or sa.shape[0] != M:                          # (before the lookup: the key holds the table's shape, not the data's M)
+            raise DasError("shift_sum: shift must be M x Mo")
         wa = None if w is None else np.ascontiguousarray(np.asarray(w))
         h = hashlib.blake2b(sa.tobytes(), digest_size=16)
         if wa is not None:
@@ -146,6 +148,12 @@ def _shift_tables(shift, w, M, dbl, cplx_data, dev, torch):
             hit = _SHIFT_MEMO.get(key)
             if hit is not None:
                 _SHIFT_MEMO.move_to_end(key)
+                # the copies belong to the allocator pool of the stream that built them: tell it that this stream reads them too, so that an evicted
+                # table is not handed out again before the call queued here has passed (no host wait: the allocator parks the block behind an event)
+                cur = torch.cuda.current_stream(dev)
+                for t in hit[:2]:
+                    if t is not None:
+                        t.record_stream(cur)
                 return hit
     sh = (shift if _is_torch(shift) else torch.from_numpy(np.asarray(shift, np.float64))).to(dev)
     if sh.ndim != 2 or sh.shape[0] != M:

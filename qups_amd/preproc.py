@@ -15,25 +15,45 @@ from . import _lib
 # Plans by shape: a qdas_pre_plan owns its twiddles -- and, for record lengths the one-pass kernel does not take (a prime factor above 13, more than 8192
 # samples), two hipFFT plans and three work buffers whose creation costs 11-15 ms (profiles/r04/general_time.txt) against 0.1-0.7 ms of transform.  A frame
 # loop calls hilbert() with ONE shape: the last few plans are kept, destroyed on eviction and at interpreter exit.
-_PLANS: "dict[tuple, tuple]" = {}           # key -> (plan handle, the plan's own lock)
+_PLANS: "dict[tuple, _Entry]" = {}          # key -> entry (plan handle, the plan's own lock, use count, dead flag)
 _PLAN_CACHE_MAX = 8
-_plans_lock = __import__("threading").Lock()      # guards the DICTIONARY only (it used to be held across execute + stream synchronisation: every hilbert() of every device and thread in a row)
+_plans_lock = __import__("threading").Lock()      # guards the DICTIONARY and the entries' use counts only (it used to be held across execute + stream synchronisation: every hilbert() of every device and thread in a row)
 
 
-def _destroy(h, lk):
-    with lk:                                      # (never under a running execute)
+class _Entry:
+    """One cached plan.  ``users`` counts the hilbert() calls between _pre_plan and _release; ``dead`` is set when the entry leaves the dictionary.  Both change
+    under _plans_lock only, and the plan is destroyed by whoever finds ``dead and users == 0``: an eviction or clear_pre_plan_cache() between a caller's
+    _pre_plan and its execute leaves the plan alive until that caller is done."""
+    __slots__ = ("h", "lock", "users", "dead")
+
+    def __init__(self, h):
+        self.h, self.lock, self.users, self.dead = h, __import__("threading").Lock(), 0, False
+
+
+def _destroy(e):
+    with e.lock:                                  # (never under a running execute)
         try:
-            _lib.lib().qdas_pre_plan_destroy(h)
+            _lib.lib().qdas_pre_plan_destroy(e.h)
         except Exception:                         # (interpreter exit: the HIP runtime may be gone before this hook runs)
             pass
 
 
+def _retire(entries):
+    """under _plans_lock: mark the entries dead; returns those nobody uses (to destroy once the lock is released)"""
+    idle = []
+    for e in entries:
+        e.dead = True
+        if e.users == 0:
+            idle.append(e)
+    return idle
+
+
 def clear_pre_plan_cache():
     with _plans_lock:
-        items = list(_PLANS.values())
+        idle = _retire(list(_PLANS.values()))
         _PLANS.clear()
-    for h, lk in items:
-        _destroy(h, lk)
+    for e in idle:
+        _destroy(e)
 
 
 def _at_exit():
@@ -47,22 +67,33 @@ __import__("atexit").register(_at_exit)
 
 
 def _pre_plan(key, d):
-    """(plan, lock) of this shape: created on a miss, the oldest entry evicted beyond _PLAN_CACHE_MAX (destroyed once no execute holds it)"""
+    """the entry of this shape with its use count raised (hand it back with _release): created on a miss, the oldest entry evicted beyond _PLAN_CACHE_MAX
+    (destroyed once no hilbert() holds it)"""
     L = _lib.lib()
-    evicted = []
     with _plans_lock:
         e = _PLANS.pop(key, None)
         if e is None:
             h = C.c_void_p()
             _lib.check(L.qdas_pre_plan_create(C.byref(h), C.byref(d)))
             hilbert.plans_created = getattr(hilbert, "plans_created", 0) + 1
-            e = (h, __import__("threading").Lock())
+            e = _Entry(h)
         _PLANS[key] = e                                              # (most recently used last)
+        e.users += 1
+        evicted = []
         while len(_PLANS) > _PLAN_CACHE_MAX:
             evicted.append(_PLANS.pop(next(iter(_PLANS))))
-    for h, lk in evicted:
-        _destroy(h, lk)
+        idle = _retire(evicted)
+    for v in idle:
+        _destroy(v)
     return e
+
+
+def _release(e):
+    with _plans_lock:
+        e.users -= 1
+        last = e.dead and e.users == 0
+    if last:
+        _destroy(e)
 
 
 def hilbert(x, N: int | None = None, fdown: float = 0.0, t0: float = 0.0, fs: float | None = None, device=None):
@@ -101,10 +132,13 @@ def hilbert(x, N: int | None = None, fdown: float = 0.0, t0: float = 0.0, fs: fl
                      dev.index if dev.index is not None else torch.cuda.current_device(), float(fs or 0.0), float(t0), float(fdown))
     L = _lib.lib()
     key = (T, K, N, int(d.in_type), int(d.device), float(d.fs), float(d.t0), float(d.fdown), __import__("os").environ.get("QDAS_PRE_HIPFFT"))      # (the switch is read at plan creation: part of the key)
-    h, plan_lock = _pre_plan(key, d)
-    with torch.cuda.device(dev), plan_lock:                         # (one execute at a time per PLAN: its hipFFT work buffers are the plan's; other shapes / devices run beside it)
-        hilbert.last_one_pass = bool(L.qdas_pre_plan_one_pass(h))   # which path served the last call (tests / tools)
-        _lib.check(L.qdas_pre_execute(h, C.c_void_p(xc.data_ptr()), C.c_void_p(y.data_ptr()),
-                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        torch.cuda.current_stream().synchronize()
+    e = _pre_plan(key, d)
+    try:
+        with torch.cuda.device(dev), e.lock:                        # (one execute at a time per PLAN: its hipFFT work buffers are the plan's; other shapes / devices run beside it)
+            hilbert.last_one_pass = bool(L.qdas_pre_plan_one_pass(e.h))   # which path served the last call (tests / tools)
+            _lib.check(L.qdas_pre_execute(e.h, C.c_void_p(xc.data_ptr()), C.c_void_p(y.data_ptr()),
+                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            torch.cuda.current_stream().synchronize()
+    finally:
+        _release(e)                                                 # (an entry evicted meanwhile is destroyed here, by its last user)
     return y.t().reshape((N,) + rest)
