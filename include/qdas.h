@@ -641,7 +641,12 @@ uint64_t qdas_pwznxcorr_lds_bytes(int dtype, int cplx, uint64_t W, uint64_t span
 /* ---- Temporaries of the stream entries (qdas_shift_sum, qdas_das_lut, qdas_greens, qdas_convd's FFT path): taken from an arena the library keeps per (device,
  * stream).  One such call at a time runs per (device, stream) -- a second thread on the same stream waits --, and a call MAY BLOCK the host: when the stream's
  * previous call outgrew the arena (the next call waits for it, then regrows the arena to what that call needed, up to 512 MiB) or asks for a single temporary above
- * 64 MiB (freed, after a stream synchronisation, when the call returns).  Otherwise the calls only enqueue work.  qdas_device_trim releases idle arenas. */
+ * 64 MiB (freed, after a stream synchronisation, when the call returns).  Otherwise the calls only enqueue work.  qdas_device_trim releases idle arenas.
+ * qdas_eikonal, qdas_adjoint and qdas_migration take their work space from the same arenas.  Two environment variables, both read per call:
+ *   QDAS_SCRATCH_ARENA_MAX_MB=<n>   the 64 MiB above (0: every temporary is a block of its own, freed when its call returns);
+ *   QDAS_SCRATCH_POISON=<0..255>    (tests; unset by default, then one getenv per temporary / plan allocation) every temporary is filled with this byte on
+ *                                   the call's stream before the call uses it, and every device allocation a plan owns (misfit-tile list, partial images,
+ *                                   fold buffers, staging) once, synchronously, when it is made: results must not depend on it. */
 
 /* ---- Device staging for HOST callers of the device-pointer entries above (qdas_delays*, qdas_das_lut, qdas_wsinterpd, qdas_greens, qdas_convd,
  * qdas_pre_execute ...): the reference reaches those kernels with gpuArrays (kern/wsinterpd2.m:236, src/UltrasoundSystem.m:681-718, kern/convd.m:150-199),

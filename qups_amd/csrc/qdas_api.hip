@@ -114,9 +114,22 @@ struct qdas_plan {
     }
 };
 
+// every device allocation of this file: hipMalloc, and -- QDAS_SCRATCH_POISON (csrc/scratch.hip scratch_poison: one getenv when unset) -- the block filled with
+// that byte before anything else touches it, synchronously.  A buffer that is then wholly uploaded or cleared is unaffected; one that a kernel reads before the
+// plan wrote it reads the poison instead of whatever hipMalloc handed back
+static hipError_t plan_malloc(void **out, size_t bytes) {
+    const hipError_t e = hipMalloc(out, bytes);
+    if (e != hipSuccess) return e;
+    const int poison = scratch_poison();
+    if (poison < 0) return hipSuccess;
+    const hipError_t m = hipMemset(*out, poison, bytes);
+    if (m != hipSuccess) { (void)hipFree(*out); *out = nullptr; }
+    return m;
+}
+
 static int dev_alloc(qdas_plan *pl, void **out, size_t bytes) {
     void *p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
+    hipError_t e = plan_malloc(&p, bytes ? bytes : 16);
     if (e != hipSuccess) return fail(QDAS_ENOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
     pl->owned.push_back(p);
     *out = p;
@@ -355,7 +368,7 @@ __global__ void mirror_map_check_kernel(const uint32_t *c, uint64_t I1, uint64_t
 static int mirror_symmetric_map(const float *dmap, uint64_t I1, uint64_t I2, bool *yes) {
     *yes = false;
     uint32_t *flag = nullptr, res = 1;
-    HIPCHK(hipMalloc((void **)&flag, sizeof(uint32_t)));
+    HIPCHK(plan_malloc((void **)&flag, sizeof(uint32_t)));
     hipError_t e = hipMemset(flag, 0, sizeof(uint32_t));
     if (e == hipSuccess) {
         const uint64_t n = I1 * (I2 / 2);
@@ -411,7 +424,7 @@ static int mirror_symmetric(const qdas_desc *desc, const float *dPi, bool *yes, 
         }
     }
     uint32_t *flag = nullptr;
-    HIPCHK(hipMalloc(&flag, 2 * sizeof(uint32_t)));
+    HIPCHK(plan_malloc((void **)&flag, 2 * sizeof(uint32_t)));
     hipError_t e = hipMemset(flag, 0, 2 * sizeof(uint32_t));
     uint32_t res[2] = {1u, 0x7f800000u};
     if (e == hipSuccess) {
@@ -553,7 +566,7 @@ static int plan_resolve_modes(qdas_plan *pl, const qdas_desc *desc, PlanBuild &b
         else if (need == modes::NEED_FOLD_BUF) {          // the plan's folded copy of a frame: without the memory for it, the plan simply does not fold
             void *fbuf = nullptr;
             f.fold_buf_known = true;
-            if (hipMalloc(&fbuf, (size_t)z.T * z.N * z.M * 8) != hipSuccess) { (void)hipGetLastError(); f.fold_buf_ok = false; }
+            if (plan_malloc(&fbuf, (size_t)z.T * z.N * z.M * 8) != hipSuccess) { (void)hipGetLastError(); f.fold_buf_ok = false; }
             else { pl->owned.push_back(fbuf); pl->fold_buf = fbuf; f.fold_buf_ok = true; }
         } else if (need == modes::NEED_MIRROR) {
             bool yes = false;
@@ -1015,7 +1028,7 @@ static void plan_f16_child(qdas_plan *pl, const qdas_desc *desc) {
     qdas_plan *child = nullptr;
     void *fb = nullptr, *yb = nullptr;
     if (qdas_plan_create(&child, &d) == QDAS_OK && child && child->kernel == QDAS_KERNEL_TILED && child->prefolded
-        && hipMalloc(&fb, (size_t)z.T * z.N * z.M * 8) == hipSuccess && hipMalloc(&yb, (size_t)child->y_ld * 8 + 16) == hipSuccess
+        && plan_malloc(&fb, (size_t)z.T * z.N * z.M * 8) == hipSuccess && plan_malloc(&yb, (size_t)child->y_ld * 8 + 16) == hipSuccess
         && hipMemset(fb, 0, (size_t)z.T * z.N * z.M * 8) == hipSuccess) {
         pl->owned.push_back(fb); pl->owned.push_back(yb);
         pl->fold_buf = fb; pl->y32 = yb; pl->f16_child = child;
@@ -1087,7 +1100,7 @@ static int plan_cache_prologue(qdas_plan *pl) {
     const size_t stride = 2 * ((size_t)t.M + t.N) + 8 + (with_mask ? (t.N + 31) / 32 : 0), bytes = (size_t)pl->ntiles * stride * sizeof(float);
     if (bytes > (1ull << 30)) return QDAS_OK;           // (thousands of elements x tens of thousands of tiles: not worth a GiB)
     void *buf = nullptr;
-    if (hipMalloc(&buf, bytes) != hipSuccess) { (void)hipGetLastError(); return QDAS_OK; }      // (no memory for it: the kernels compute their tables themselves)
+    if (plan_malloc(&buf, bytes) != hipSuccess) { (void)hipGetLastError(); return QDAS_OK; }      // (no memory for it: the kernels compute their tables themselves)
     pl->owned.push_back(buf);
     TileParams p = t;
     p.probe = 1; p.x = nullptr; p.y = nullptr; p.wtab = nullptr; p.apix = nullptr; p.pro_out = (float *)buf; p.pro_mask = with_mask ? 1 : 0;
@@ -1382,7 +1395,7 @@ static int prepare_stream(qdas_plan *pl, uint64_t F, hipStream_t s) {
     if (pl->fold2_ok && !pl->prefolded && !pl->fold_buf2) {
         const size_t fb = (size_t)z.T * z.N * z.M * 8;
         void *p2 = nullptr;
-        if (hipMalloc(&p2, fb) == hipSuccess) {
+        if (plan_malloc(&p2, fb) == hipSuccess) {
             pl->owned.push_back(p2);
             if (hipMemsetAsync(p2, 0, fb, s) == hipSuccess) pl->fold_buf2 = p2;
         } else (void)hipGetLastError();
@@ -1541,7 +1554,7 @@ extern "C" int qdas_plan_delays(qdas_plan *pl, void *tau, void *stream) {
     const size_t bytes = (size_t)pl->i_count * z.N * z.M * rs;
     if (pl->d.mem == QDAS_MEM_HOST) {
         void *dt;
-        HIPCHK(hipMalloc(&dt, bytes));
+        HIPCHK(plan_malloc(&dt, bytes));
         hipError_t e = launch_delays(g, z.dtype == QDAS_F64 ? 0 : 1, dt, cinv, s);
         if (e == hipSuccess) e = hipMemcpyAsync(tau, dt, bytes, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);

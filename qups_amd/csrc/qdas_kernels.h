@@ -130,6 +130,10 @@ private:
     std::vector<void *> big_;
 };
 void scratch_trim();
+// QDAS_SCRATCH_POISON=<byte value 0..255> (read per call, unset by default: one getenv): the byte every block of Scratch::get and every plan-owned device
+// allocation is filled with before anything of the library writes it; -1: unset.  The tests' switch (tests/test_gpu_scratch.py): a temporary that is read
+// before its own call wrote it then reads this byte instead of whatever the last call left there
+int scratch_poison();
 
 // ---- batched 1-D convolution (conv.hip)
 struct ConvParams {

@@ -42,6 +42,14 @@ Arena *arena_of(int dev, hipStream_t s) {
 size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 }  // namespace
 
+int scratch_poison() {
+    const char *e = getenv("QDAS_SCRATCH_POISON");
+    if (!e || !*e) return -1;
+    char *end = nullptr;
+    const long v = strtol(e, &end, 0);
+    return (end != e && *end == 0 && v >= 0 && v <= 255) ? (int)v : -1;
+}
+
 Scratch::Scratch(hipStream_t s) : stream_(s) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
@@ -60,6 +68,7 @@ Scratch::Scratch(hipStream_t s) : stream_(s) {
     }
 }
 
+// (QDAS_SCRATCH_POISON: the block -- arena, per-call or never-kept -- is filled on the call's stream before it is handed out; rounded up to the 256 bytes it owns)
 void *Scratch::get(size_t bytes) {
     Arena *a = (Arena *)arena_;
     const size_t b = up256(bytes ? bytes : 1);
@@ -68,16 +77,18 @@ void *Scratch::get(size_t bytes) {
     if (b > ARENA_MAX) {                                 // never kept
         if (hipMalloc(&p, b) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         big_.push_back(p);
-        return p;
+    } else if (off_ + b <= a->cap) { p = (char *)a->base + off_; off_ += b; }
+    else {
+        off_ += b;
+        // the arena regrows to the call's real total (clamped to ARENA_MAX, a call whose SMALL requests add up to more overflowed on every call -- a stream
+        // synchronisation, hipFree and hipMalloc per call: the churn the arena exists to remove); a total beyond 8 x ARENA_MAX is not kept: that call pattern keeps the
+        // per-call blocks, and each such call begins by waiting for the stream's previous one (include/qdas.h: one-shot entries may block)
+        if (off_ > a->want && off_ <= 8 * ARENA_MAX) a->want = off_;
+        if (hipMalloc(&p, b) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        a->extra.push_back(p);
     }
-    if (off_ + b <= a->cap) { p = (char *)a->base + off_; off_ += b; return p; }
-    off_ += b;
-    // the arena regrows to the call's real total (clamped to ARENA_MAX, a call whose SMALL requests add up to more overflowed on every call -- a stream
-    // synchronisation, hipFree and hipMalloc per call: the churn the arena exists to remove); a total beyond 8 x ARENA_MAX is not kept: that call pattern keeps the
-    // per-call blocks, and each such call begins by waiting for the stream's previous one (include/qdas.h: one-shot entries may block)
-    if (off_ > a->want && off_ <= 8 * ARENA_MAX) a->want = off_;
-    if (hipMalloc(&p, b) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    a->extra.push_back(p);
+    const int poison = scratch_poison();
+    if (poison >= 0 && hipMemsetAsync(p, poison, b, stream_) != hipSuccess) { (void)hipGetLastError(); return nullptr; }      // (the block stays with big_ / extra: freed as usual)
     return p;
 }
 
@@ -109,3 +120,17 @@ void scratch_trim() {
 }
 
 }  // namespace qdas
+
+// (tests: a block of `bytes` from the arena of `stream`, its first and last byte -- of the 256-byte multiple it owns -- copied to the host.  Shows that
+//  QDAS_SCRATCH_POISON reaches the arena, overflow and never-kept paths of Scratch::get; without the switch the bytes are whatever the block held)
+extern "C" int qdas_debug_scratch_peek(size_t bytes, void *stream, unsigned char *first, unsigned char *last) {
+    if (!first || !last) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    qdas::Scratch scratch(s);
+    const size_t b = (bytes ? bytes + 255 : 256) / 256 * 256;
+    unsigned char *p = (unsigned char *)scratch.get(bytes);
+    if (!p) return 2;
+    if (hipMemcpyAsync(first, p, 1, hipMemcpyDeviceToHost, s) != hipSuccess || hipMemcpyAsync(last, p + b - 1, 1, hipMemcpyDeviceToHost, s) != hipSuccess
+        || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return 3; }
+    return 0;
+}

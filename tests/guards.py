@@ -12,7 +12,7 @@ Three properties a parity test cannot see, each checked from the host with plain
 
 Limits: the bands are 64 KiB wide (a wilder store is not seen); an INTEGER output that legitimately holds -1 (all bits set) reads as
 "never written" -- no wrapper returns integers today; the library's own arenas and plan scratch are not torch tensors
-and are not guarded; an out-of-bounds READ whose value is discarded (masked by select) is invisible -- by design, that is legal."""
+(tests/test_gpu_scratch.py poisons them through QDAS_SCRATCH_POISON instead); an out-of-bounds READ whose value is discarded (masked by select) is invisible -- by design, that is legal."""
 from __future__ import annotations
 
 import contextlib

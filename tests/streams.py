@@ -15,7 +15,8 @@ right answer there.  torch's pool streams are non-blocking: on them such a step 
 * ``interleaved(calls, s1, s2)``: calls of growing and shrinking size issued alternately on two streams behind a filler on both, the assignment swapped between
   repetitions, each result compared bit for bit with the same call issued alone.  A temporary shared between the two streams is caught by this ONLY WITH SOME
   PROBABILITY per run: both streams must be inside the colliding steps at the same time.  The delayed producer is the deterministic check; this one adds
-  coverage of per-stream arenas and plan-owned work buffers that no input or output reaches.
+  coverage of per-stream arenas and plan-owned work buffers that no input or output reaches (what such memory carries from one call to the next ON ONE
+  stream is the subject of tests/test_gpu_scratch.py: poisoned arenas and plan scratch, entries in each other's wake, plans after a NaN frame).
 
 Out of reach: inputs a wrapper takes as HOST arrays (geometry, delay tables, filters, weights -- the list in tests/test_gpu_guards.py's halo section): they are
 uploaded by the wrapper itself and have no producer to delay."""

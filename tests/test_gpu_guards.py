@@ -14,7 +14,8 @@
 3. Isolation.  Where outputs separate by construction (kept dimensions, one image per transmit, one value per pixel), a NaN / Inf trace must change
    nothing but its own slice, bit for bit: "select, not multiply".
 
-Not covered: the library's own arenas (csrc/scratch.hip) and plan scratch are not torch tensors; stores further than 64 KiB from the output."""
+The library's own arenas (csrc/scratch.hip) and plan scratch are not torch tensors: tests/test_gpu_scratch.py poisons them instead.  Not covered: stores
+further than 64 KiB from the output."""
 import collections
 import functools
 import os

@@ -18,8 +18,9 @@ Rows marked ``inter`` also go through ``streams.interleaved`` (probabilistic for
 FILL_MS: the largest host wall time of a warm wrapper call on the default stream, measured on the MI355X inside this module (``QDAS_STREAMS_MEASURE=1`` reports
 every case's and asserts no early return; every run prints them), was 1.56 ms (migration-compose; 1.46 and 0.91 ms, bfAdjoint, in two later runs); FILL_MS is ten
 times that, rounded up: 16.  The interleaved groups and the eviction test queue several wrapper calls behind one filler and take one FILL_MS per call.
-103 tests: 82 table rows through the delayed producer, 12 interleaved groups, 9 further tests; 69 s for this file alone on the MI355X, 50 s of it the warm-up of
-every GPU session, so about 20 s on top of the suite.
+111 tests: 90 table rows through the delayed producer (eight of them added for tests/test_gpu_scratch.py, which reuses this table: scratch layouts no earlier
+row reached), 12 interleaved groups, 9 further tests; 69 s for this file alone on the MI355X with 82 rows, 50 s of it the warm-up of every GPU session, so
+about 20 s on top of the suite.
 
 What this cannot see: inputs handed over as host arrays (geometry, delay tables, filters, weights); concurrent use of one plan from two streams without an
 event between them, which the header does not promise."""
@@ -235,7 +236,8 @@ def _frames(cid, F, prepared):
             assert a.folded and b.folded
             if prepared:
                 b.prepare_frames(F)
-            yield dict(fn=lambda x: b.execute_colmajor(x, F), ref_fn=lambda x: a.execute_colmajor(x, F), tensors=[xc], warm=False)
+            yield dict(fn=lambda x: b.execute_colmajor(x, F), ref_fn=lambda x: a.execute_colmajor(x, F), tensors=[xc], warm=False,
+                       frames=F, plan=b, fresh=lambda: DasPlan(prob, kernel=2))
 
 
 for _F in (2, 4):
@@ -260,11 +262,41 @@ def _frames_twin(cid, prepared):
             assert a.mirror and b.mirror and not a.reciprocal
             if prepared:
                 b.prepare_frames(4)
-            yield dict(fn=lambda x: b.execute_colmajor(x, 4), ref_fn=lambda x: a.execute_colmajor(x, 4), tensors=[xc], warm=False)
+            yield dict(fn=lambda x: b.execute_colmajor(x, 4), ref_fn=lambda x: a.execute_colmajor(x, 4), tensors=[xc], warm=False,
+                       frames=4, plan=b, fresh=lambda: DasPlan(prob, kernel=2))
 
 
 _frames_twin("das-frames4-twin-prepared", True)
 _frames_twin("das-frames4-twin-first", False)
+
+
+@case("das-mirror", "das_plan")
+def _b():
+    """ONE frame through a general-mode lateral-mirror plan (the frames4-twin rows above send theirs through the twin, which has no mirror mode): two window
+    sets, and -- few tiles -- a split aperture whose partial images hold both halves of the image"""
+    from qups_amd import DasPlan
+    from qups_amd.das_spec import _colmajor
+    cs = make_case(seq="PW", interp="cubic", seed=12, N=16, M=8, I1=80, I2=24)
+    with DasPlan(_mk_prob(cs, "cubic", "single"), kernel=2) as plan:
+        assert plan.kernel == "tiled" and plan.mirror and not plan.reciprocal
+        xc = _colmajor(torch.from_numpy(cs["x"]).cuda())
+        yield dict(fn=lambda x: plan.execute_colmajor(x.reshape(1, *x.shape), 1), tensors=[xc])
+
+
+@case("das-misfit", "das_plan")
+def _b():
+    """tests/test_gpu_parity.py test_oversize_window_falls_back: 49 samples of delay per pixel -- tiles that fit no window are listed by the fused kernel in the
+    plan's fallback list and redone by the generic kernel behind it (and behind the reduce of the split aperture, which reads their unwritten partial images)"""
+    from qups_amd import DasPlan
+    from qups_amd.das_spec import _cast_data, _colmajor
+    cs = make_case(seq="PW", interp="cubic", seed=16, I1=60, I2=6, zlim=(2e-3, 120e-3), data="noise", N=8, M=4)
+    with DasPlan(_mk_prob(cs, "cubic", "single"), kernel=0) as plan:
+        xc = _colmajor(_cast_data(torch.from_numpy(cs["x"]), "single", plan.device))
+        fn = lambda x: plan.execute_colmajor(x.reshape(1, *x.shape), 1)
+        fn(xc)
+        torch.cuda.synchronize()                               # (fallback_tiles reads the count the last frame left in the list)
+        assert plan.kernel == "tiled" and plan.fallback_tiles() > 0 and plan.aperture_split() > 1, (plan.kernel, plan.fallback_tiles(), plan.aperture_split())
+        yield dict(fn=fn, tensors=[xc])
 
 
 @case("plan_execute_abi", "das_plan")
@@ -399,6 +431,45 @@ _lut("das_lut-tx", False, True, "single", inter="das_lut")
 _lut("das_lut-rxtx", True, True, "single")
 
 
+def lut_mirror_tables(a_rx, a_tx, lat, I1=140, I2=40, N=32, M=32):
+    """synthetic split-delay tables in SAMPLES (float32, I1 x I2 x N and I1 x I2 x M) that are their own lateral mirror images: a depth slope ``a * i1``, a
+    lateral term ``lat * column`` and a small offset per element in the first half of the columns; the second half is the exact mirror image of the first
+    (tests/test_gpu_golden.py test_das_lut_mirror_symmetric_tables_take_the_mirror_mode).  Inside a tile of R rows and C columns every element's delays
+    spread over ``a (R - 1) + lat (C - 1)`` samples: what the window-fit rule of csrc/tile_prologue.h sees."""
+    assert I2 % 2 == 0
+    i1, c = np.arange(I1, dtype=np.float64)[:, None, None], np.arange(I2, dtype=np.float64)[None, :, None]
+    mk = lambda a, E: (4.0 + a * i1 + lat * c + 0.03 * np.arange(E, dtype=np.float64)[None, None, :]).astype(np.float32)
+    rx, tx = mk(a_rx, N), mk(a_tx, M)
+    h = I2 // 2
+    rx[:, -h:, :] = rx[:, :h, :][:, ::-1, ::-1]
+    tx[:, -h:, :] = tx[:, :h, :][:, ::-1, ::-1]
+    return rx, tx
+
+
+def lut_mirror_data(T=1024, N=32, M=32):
+    rng = np.random.default_rng(61)
+    return (rng.standard_normal((T, N, M)) + 1j * rng.standard_normal((T, N, M))).astype(np.complex64)
+
+
+@case("das_lut-mirror", "das_lut")
+def _b():
+    """the mirror build of qdas_das_lut (fp32, full sum, no weights, kM >= 32; exists as a hiprtc build only): 6 tiles of the half image, so eight workgroups per
+    tile and partial images (ks2 = 8) from the arena behind the misfit counter and the symmetry flag"""
+    from qups_amd.interpd import das_lut
+    rx, tx = lut_mirror_tables(0.5, 0.5, 0.05)
+    x, n1, n2 = _dev(lut_mirror_data()), _dev(rx), _dev(tx)
+
+    def fn(xx, a, b):
+        y = das_lut(xx, a, b, interp="cubic", prec="single")
+        fn.kernel = das_lut.last_kernel
+        return y
+    fn(x, n1, n2)
+    torch.cuda.synchronize()
+    if "mirror" not in fn.kernel:                              # (no hiprtc on this box: the mode exists as a specialised build only)
+        pytest.skip("no mirror build: " + fn.kernel)
+    yield dict(fn=fn, tensors=[x, n1, n2], route="tiled,mirror")
+
+
 def _ws(cid, M, sdim):
     @case(cid, "wsinterpd", inter="wsinterpd")
     def _b():
@@ -447,6 +518,24 @@ _shift("shift_sum-host-tables", True)          # a memo hit after the warm calls
 _shift("shift_sum-device-tables", False)
 
 
+def _shift64(cid, weights):
+    @case(cid, "shift_sum")
+    def _b():
+        """fp64 data: table entries of 56 instead of 28 bytes in the stream's arena, with and without a weight table"""
+        from qups_amd.interpd import shift_sum
+        from tests import test_gpu_guards as TG
+        x, shift, w, pad = TG._shift_case("complex128")
+        T = x.shape[0]
+        if weights:
+            yield dict(fn=lambda xx, s, ww: shift_sum(xx, s, ww, "cubic", To=T + 17, tpad=pad), tensors=[_dev(x), _dev(shift), _dev(w)])
+        else:
+            yield dict(fn=lambda xx, s: shift_sum(xx, s, None, "cubic", To=T + 17, tpad=pad), tensors=[_dev(x), _dev(shift)])
+
+
+_shift64("shift_sum-double", True)
+_shift64("shift_sum-double-noweights", False)
+
+
 # ================================================================================================================ greens, convd, iir, hilbert
 def _greens(prec):
     @case(f"greens-{prec}", "greens", inter="greens")
@@ -461,6 +550,33 @@ def _greens(prec):
 
 _greens("single")
 _greens("double")
+
+
+def _greens_trains(cid, I):
+    @case(cid, "greens")
+    def _b():
+        """the impulse-train kernels (QDAS_GREENS_TRAIN_MIN=0, read per call): distance tables, chunk bounds, tap list in the stream's arena -- and, from 4096
+        scatterers on, the Morton sort's keys, histogram and sorted copies.  The trains are integer sums: bit-reproducible."""
+        from qups_amd.greens import greens_kernel
+        from tests.test_greens import _setup
+        g = _setup(seed=5, N=9, M=7, I=I, En=2, Em=3, fsr=1.0)
+        args = (g["Ps"], g["a"], g["Pr"], g["Pv"], g["x"], g["S"], g["s0"], g["t0"], g["fs"], 1.0, g["cinv"], g["R0"], "linear")
+
+        def fn(train_min="0"):
+            old = os.environ.get("QDAS_GREENS_TRAIN_MIN")
+            os.environ["QDAS_GREENS_TRAIN_MIN"] = train_min
+            try:
+                return greens_kernel(*args, "single")
+            finally:
+                if old is None:
+                    del os.environ["QDAS_GREENS_TRAIN_MIN"]
+                else:
+                    os.environ["QDAS_GREENS_TRAIN_MIN"] = old
+        yield dict(fn=fn, tensors=[])
+
+
+_greens_trains("greens-trains", 300)                  # two chunks of 256 scatterers, the second ragged; no sort
+_greens_trains("greens-trains-sorted", 4100)          # the sort / gather pass (>= 4096 scatterers), 17 chunks, the last ragged
 
 
 @case("convd-direct", "convd", inter="convd")
@@ -570,6 +686,22 @@ def _b():
     c = R.smooth_random(17, 33, seed=17 + 3300)
     sets = [[[1.0], [1.0]], [[17.0], [33.0]]]
     yield dict(fn=lambda cc: H._solve(cc, H.DP, sets).contiguous(), tensors=[_dev(c)])
+
+
+@case("eikonal-chunks", "eikonal")
+def _b():
+    """a map of 3 x 5 tiles: the fronts need more passes than one chunk of four (csrc/eikonal.hip CHUNK), so the chunk's counters are cleared and reused"""
+    from qups_amd import eikonal as E
+    from tests import eikonal_ref as R
+    from tests import test_gpu_eikonal as H
+    c = R.smooth_random(40, 70, seed=40 + 7000)
+    sets = [[[1.0], [1.0]], [[40.0], [70.0]]]
+
+    def fn(cc):
+        T = H._solve(cc, H.DP, sets).contiguous()
+        assert E.last_passes() > 4, E.last_passes()
+        return T
+    yield dict(fn=fn, tensors=[_dev(c)])
 
 
 def _eik_tables(cid, npix, inter):
