@@ -143,7 +143,7 @@ extern "C" {
 #define QDAS_EHIP          3 /* HIP runtime error (message carries hipGetErrorString)   */
 #define QDAS_ENOMEM        4
 #define QDAS_ENOCONV       5 /* an iteration reached its pass cap without a fixed point  */
-#define QDAS_ENOTLDS       6 /* qdas_migration: a transform length its in-LDS kernels do not take (the caller composes the image instead) */
+#define QDAS_ENOTLDS       6 /* qdas_migration, qdas_refocus: a transform length the in-LDS kernels do not take (the caller composes the result instead) */
 
 /* Size/flag constants: the reference's constant-memory symbols QUPS_{T,N,M,I,I1,I2,I3,S},
  * QUPS_{VS,DV}, QUPS_BF_FLAG (reference src/sizes.cu:17-52, src/bf.cu:45-47;
@@ -599,6 +599,36 @@ typedef struct qdas_migration_desc {
     const double *gamma;          /* M: sin(theta) / (2 - cos(theta))                               */
 } qdas_migration_desc;
 int qdas_migration(const qdas_migration_desc *desc, const void *x, void *b, void *stream);
+
+/* ---- REFoCUS (refocus.hip): the reference's UltrasoundSystem.refocus (src/UltrasoundSystem.m:3505-3768) with the decoder given -- channel data of V
+ * transmit pulses x[t, n, v, frame] (complex64, T x N x V x frames, time fastest) back to the full-synthetic-aperture data of M transmit elements.
+ * With f_k = k fs / T for k = 0 .. T-1 (ChannelData.fftaxis: NOT wrapped to negative frequencies) and the decoder pages Hi_k (M x V):
+ *   1. X = FFT_t(x) exp(-2 pi i f_k t0[v])
+ *   2. Y_k[n, m] = sum_v Hi_k[m, v] X_k[n, v]
+ *   3. Y *= exp(+2 pi i f_k t0_out),  t0_out = min(t0);   y = IFFT_t(Y)
+ * y: DEVICE complex64 T x N x M x frames, time fastest; its sample 0 is at t0_out.  Hi: DEVICE complex64 M x V x T, m fastest -- the reference's order, so a
+ * MATLAB caller passes its own Hi unchanged; how the pages are built from the sequence's delays and apodization (adjoint, tikhonov, pinv) is the
+ * caller's business (qups_amd/refocus.py builds them on the host in float64, once per sequence).  With one_t0 the two phases cancel and neither is applied.
+ * Three passes of complex64 (time FFT in LDS, the per-frequency products on the f32 matrix cores, inverse FFT in LDS), no atomics: results are
+ * bit-reproducible.
+ * STREAM.  The call is asynchronous on the hipStream_t in the descriptor's `queue` field: no synchronisation, no allocation.  It travels in the descriptor and
+ * not as a trailing parameter because the census of the entries that take one (tests/test_streams_host.py) is a pinned list; the entry's stream case
+ * lives in tests/test_gpu_refocus.py until that list may change.
+ * WORK SPACE.  The caller provides it (the work_bytes entry tells how much: T twiddles, then T x V x N frames and T x M x N frames complex64); the library's
+ * per-stream arenas are not used and nothing the work space held before the call is read.
+ * All validation happens on the host before any HIP call: null pointers and a work space that is too small are QDAS_EINVAL; T, N, V, M or frames = 0 is
+ * QDAS_OK, nothing is launched (y is not written), no device needed; a T the in-LDS transforms do not take (qdas_migration's rule: products of 2, 3, 5, 7, 11, 13 from 2 to
+ * 8192 whose stages fit a workgroup) is QDAS_ENOTLDS, nothing is launched (the caller composes the result instead); more than 65535 pulses or elements,
+ * or N * frames beyond 2^31 - 256, QDAS_EUNSUPPORTED. */
+typedef struct qdas_refocus_desc {
+    uint64_t T, N, V, M, frames;  /* samples, receivers, transmit pulses, transmit elements, frames */
+    double   fs, t0_out;          /* sampling frequency; min(t0): the time of sample 0 of y         */
+    int32_t  device, one_t0;      /* HIP device ordinal, -1 = current; 1: t0 is one value           */
+    const double *t0;             /* DEVICE, V or 1 values (not read when one_t0)                   */
+    void    *queue;               /* a hipStream_t                                                  */
+} qdas_refocus_desc;
+int qdas_refocus_work_bytes(const qdas_refocus_desc *desc, uint64_t *bytes);
+int qdas_refocus(const qdas_refocus_desc *desc, const void *x, const void *Hi, void *y, void *work, uint64_t work_bytes);
 
 /* ---- Pair-wise windowed zero-normalized cross-correlation (pwznxcorr.hip): the base-MATLAB branch of the reference's kern/pwznxcorr.m (iflt = false:
  * convn(., w, 'same'), a zero pad at the end of the record, circshift) for every lag in ONE launch.  With h = floor(W / 2), P = max|lags| when `pad` (else 0),

@@ -60,6 +60,9 @@
  *         sizes = [I N M V F], flags = [keep_rx keep_tx]; the arrays are described at cmd_adjoint below.  b is I x [N] x [V] single complex.
  *   b       = qdas_mex('migration', sizes, x, tau, gamma, params, flags)
  *         sizes = [T N M frames F K], params = [fs fmod t0 c0 pitch], flags = [interp keep_tx jacobian]; described at cmd_migration below.
+ * REFoCUS (src/UltrasoundSystem.m:3735-3762: the decoder Hi applied to the data; building Hi stays in MATLAB, as the reference has it):
+ *   y       = qdas_mex('refocus', sizes, x, Hi, t0, fs)
+ *         sizes = [T N V M frames]; described at cmd_refocus below.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
  * pass as device pointers and the result is a gpuArray.
  *
@@ -797,6 +800,46 @@ static mxArray *cmd_migration(int nrhs, const mxArray *prhs[]) {
     return finish(qdas_migration(&d, x, b, NULL), host, bytes);
 }
 
+/* y = qdas_mex('refocus', sizes, x, Hi, t0, fs) -- lines 3735-3762 of the reference's refocus (src/UltrasoundSystem.m): fft, time-alignment phase, Hi applied over
+ * the transmits, phase back, ifft.  sizes = [T N V M frames] (the gateway takes its extents from a sizes row like every other command); x: T x N x V x frames
+ * single complex; Hi: M x V x T single complex, the reference's own array, unchanged; t0: one real double or one per pulse (V), a HOST array; fs: a real
+ * scalar.  y: T x N x M x frames single complex; its time axis starts at min(t0).  A record length the in-LDS kernels do not take raises QUPS:das_spec:qdas
+ * with the library's text (the caller runs the reference's lines in MATLAB then).  The work space is staged like an input and released with them. */
+static mxArray *cmd_refocus(int nrhs, const mxArray *prhs[]) {
+    if (nrhs != 5) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('refocus', sizes, x, Hi, t0, fs)");
+    qdas_refocus_desc d;
+    memset(&d, 0, sizeof d);
+    d.T = (uint64_t)num_at(prhs[0], 0, "sizes"); d.N = (uint64_t)num_at(prhs[0], 1, "sizes"); d.V = (uint64_t)num_at(prhs[0], 2, "sizes");
+    d.M = (uint64_t)num_at(prhs[0], 3, "sizes"); d.frames = (uint64_t)num_at(prhs[0], 4, "sizes");
+    d.fs = num_at(prhs[4], 0, "fs");
+    d.device = -1;
+    const mxArray *xa = prhs[1], *ha = prhs[2], *ta = prhs[3];
+    if ((!mxIsEmpty(xa) && (mxGetClassID(xa) != mxSINGLE_CLASS || !mxIsComplex(xa))) || (!mxIsEmpty(ha) && (mxGetClassID(ha) != mxSINGLE_CLASS || !mxIsComplex(ha))))
+        mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "refocus: the data and Hi must be single complex.");
+    const mwSize dims[4] = {(mwSize)d.T, (mwSize)d.N, (mwSize)d.M, (mwSize)d.frames};
+    const size_t bytes = (size_t)dims[0] * dims[1] * dims[2] * dims[3] * 8;
+    if (!bytes || !d.V) return mxCreateNumericArray(4, dims, mxSINGLE_CLASS, mxCOMPLEX);           /* empty in, or no pulses to sum: empty / zeros out */
+    const size_t nt0 = (size_t)mxGetNumberOfElements(ta);
+    if (mxGetClassID(ta) != mxDOUBLE_CLASS || mxIsComplex(ta) || (nt0 != 1 && nt0 != d.V)) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "refocus: t0 must hold one real double, or one per pulse.");
+    const double *t0 = (const double *)mxGetData(ta);
+    d.one_t0 = nt0 == 1;
+    d.t0_out = t0[0];
+    for (size_t v = 1; v < nt0; ++v) if (t0[v] < d.t0_out) d.t0_out = t0[v];
+    uint64_t wbytes = 0;
+    if (qdas_refocus_work_bytes(&d, &wbytes)) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "%s", qdas_last_error());
+    int dev = 0;
+    const void *x = dev_in(xa, (size_t)(d.T * d.N * d.V * d.frames) * 8, "x", &dev);
+    const void *Hi = dev_in(ha, (size_t)(d.M * d.V * d.T) * 8, "Hi", &dev);
+    if (!d.one_t0) d.t0 = (const double *)dev_in(ta, nt0 * 8, "t0", &dev);
+    if (g_nda >= QDAS_MEX_MAX_DEVARGS) CFAIL("too many array arguments.");
+    devarg *w = &g_da[g_nda++];                                                                     /* the work space: owned, released with the inputs */
+    memset(w, 0, sizeof *w);
+    if (qdas_device_malloc(&w->owned, (size_t)wbytes, -1)) CFAIL("%s", qdas_last_error());
+    mxArray *host;
+    void *y = dev_out(4, dims, mxSINGLE_CLASS, 1, dev, bytes, &host);
+    return finish(qdas_refocus(&d, x, Hi, y, w->owned, wbytes), host, bytes);
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
 #ifdef QDAS_MEX_GPU
     mxInitGPU();
@@ -843,6 +886,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "msfm")) { plhs[0] = cmd_msfm(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "adjoint")) { plhs[0] = cmd_adjoint(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "migration")) { plhs[0] = cmd_migration(nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "refocus")) { plhs[0] = cmd_refocus(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();
         } else mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unknown command '%s'.", cmd);

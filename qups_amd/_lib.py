@@ -38,7 +38,7 @@ SYMBOLS = (
     "qdas_plan_destroy_sharded", "qdas_DAS", "qdas_DASf", "qdas_DASh", "qdas_delays", "qdas_delaysf",
     "qdas_das_lut", "qdas_das_lut_last_kernel", "qdas_wsinterpd", "qdas_shift_sum", "qdas_greens", "qdas_convd", "qdas_convd_len", "qdas_permute3", "qdas_pre_plan_create", "qdas_pre_execute", "qdas_pre_plan_destroy", "qdas_pre_plan_one_pass", "qdas_last_error", "qdas_version", "qdas_device_malloc", "qdas_device_free", "qdas_device_trim", "qdas_device_copy", "qdas_iir", "qdas_device_info", "qdas_kernel_variant_build", "qdas_kernel_variant_prebuilt",
     "qdas_coherence", "qdas_eikonal", "qdas_eikonal_tables", "qdas_eikonal_last_passes", "qdas_eikonal_pass_cap", "qdas_adjoint", "qdas_migration",
-    "qdas_pwznxcorr", "qdas_pwznxcorr_time_tile", "qdas_pwznxcorr_lds_bytes",
+    "qdas_pwznxcorr", "qdas_pwznxcorr_time_tile", "qdas_pwznxcorr_lds_bytes", "qdas_refocus", "qdas_refocus_work_bytes",
 )
 
 
@@ -139,6 +139,12 @@ class PwznxcorrDesc(C.Structure):
                 ("y_strideN", C.c_int64), ("y_bstride", C.c_int64 * 2), ("y_strideL", C.c_int64)]
 
 
+class RefocusDesc(C.Structure):
+    _fields_ = [("T", C.c_uint64), ("N", C.c_uint64), ("V", C.c_uint64), ("M", C.c_uint64), ("frames", C.c_uint64),
+                ("fs", C.c_double), ("t0_out", C.c_double), ("device", C.c_int32), ("one_t0", C.c_int32),
+                ("t0", C.c_void_p), ("queue", C.c_void_p)]
+
+
 class QdasError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libqdas error {code}: {msg}")
@@ -208,6 +214,8 @@ def lib():
     L.qdas_pwznxcorr_time_tile.argtypes = []
     L.qdas_pwznxcorr_lds_bytes.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64]
     L.qdas_pwznxcorr_lds_bytes.restype = C.c_uint64
+    L.qdas_refocus_work_bytes.argtypes = [C.POINTER(RefocusDesc), C.POINTER(C.c_uint64)]
+    L.qdas_refocus.argtypes = [C.POINTER(RefocusDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64
     L.qdas_shift_sum.argtypes = [C.POINTER(ShiftDesc), C.c_void_p, C.c_void_p, C.c_void_p]

@@ -445,6 +445,51 @@ class UltrasoundSystem:
         z = z.reshape((T2, N, Mp) + tuple(d.shape[3:]))
         return ChannelData(z, t0, chd.fs, "TNM")
 
+    def refocus(self, chd: ChannelData, seq: Sequence | None = None, gamma=None, method="tikhonov"):
+        """``[chd, Hi] = refocus(us, chd, seq, 'gamma', gamma, 'method', method)`` (reference ``src/UltrasoundSystem.m:3505-3768``): the inverse of
+        ``focusTx`` -- data recorded with the ``V`` pulses of ``seq`` (default ``us.seq``) back to the full-synthetic-aperture data of the ``M`` transmit
+        elements, by a per-frequency decoding matrix.  ``method``: ``'tikhonov'`` (default; ``gamma`` defaults to ``10 (chd.N / 10)^2`` and is scaled by the
+        largest singular value per frequency), ``'adjoint'`` (enough for plane waves and orthogonal codes) or ``'pinv'`` (not recommended).  Returns the
+        ``ChannelData`` (``T x N x M x frames...`` complex, ``t0 = min(chd.t0)``) and ``Hi`` (``M x V x T`` complex128, host).  The formulas are in
+        ``qups_amd/refocus.py``; the decoder of the last ``(delays, apodization, T, fs, method, gamma)`` is kept, so a stream of frames builds it once.
+
+        Zero-pad first.  A focused sequence has t = 0 at each focus, FSA data at each transmitting element, so the recovered echoes move in time while
+        the time axis stays as it is; and since the decoding works on the record's spectrum, whatever moves past either end of the record wraps around
+        to the other.  The record must therefore already span the times the FSA echoes will occupy: if they reach 40 us and ``chd`` ends at 20 us,
+        ``chd.zeropad(0, ceil(fs * 20e-6))`` before the call."""
+        import torch
+        from . import refocus as RF
+        if not isinstance(chd, ChannelData):
+            raise DasError("refocus: chd must be one ChannelData")
+        if method not in RF.METHODS:
+            raise DasError(f"refocus: method must be one of {RF.METHODS}, got {method!r}")
+        seq = seq or self.seq
+        chd = chd.rectifyDims()
+        x = chd._torch_data()
+        if x.ndim < 3:
+            x = x.reshape(tuple(x.shape) + (1,) * (3 - x.ndim))
+        T, N, V = (int(v) for v in x.shape[:3])
+        tau = np.asarray(seq.delays(self.tx), float)               # M x V
+        apd = np.broadcast_to(np.asarray(seq.apodization(self.tx), float), tau.shape)
+        if tau.shape[1] != V:
+            raise DasError(f"Number of transmits ({V}) must match the sequence's delays ({tau.shape[0]} x {tau.shape[1]}).")
+        gamma = RF.default_gamma(N) if gamma is None else float(gamma)
+        if not gamma >= 0:
+            raise DasError("refocus: gamma must be non-negative")
+        if not x.is_cuda:
+            if not torch.cuda.is_available():
+                raise RuntimeError("qups_amd: no HIP device visible -- refocus has no CPU fallback")
+            x = x.cuda()
+        key = (tau.shape, tau.tobytes(), apd.tobytes(), T, float(chd.fs), method, gamma if method == "tikhonov" else None)
+        kept = getattr(self, "_refocus_decoder", None)
+        if kept is None or kept[0] != key:
+            # the Decoder this replaces may still be read by a call queued on another stream: every use of its device copy has recorded the
+            # stream that reads it (Decoder.on), so the allocator holds the block back until those calls have passed
+            kept = (key, RF.Decoder(RF.decoder(tau, apd, T, chd.fs, method, gamma)))
+            self._refocus_decoder = kept
+        y, t0, Hi = RF.refocus(x, np.asarray(chd.t0, float).reshape(-1), chd.fs, decoder=kept[1])
+        return ChannelData(y, t0, chd.fs, "TNM"), Hi
+
     # ------------------------------------------------------------------------------------
     def delay_tables(self, c0=None, device=None):
         """``tau_rx (I1 x I2 x I3 x N)``, ``tau_tx (I1 x I2 x I3 x M)`` as ``bfDAS`` computes them
