@@ -630,6 +630,36 @@ typedef struct qdas_refocus_desc {
 int qdas_refocus_work_bytes(const qdas_refocus_desc *desc, uint64_t *bytes);
 int qdas_refocus(const qdas_refocus_desc *desc, const void *x, const void *Hi, void *y, void *work, uint64_t work_bytes);
 
+/* ---- Straight-ray integrals over a rectilinear grid (raypaths.hip): the reference's kern/wbilerpg.m (bilinear ray weights), kern/rayPaths.m (the tomography
+ * system matrix) and kern/globalAverageC.m (the integral of a slowness map along straight rays).  The grid vectors xg (X values) and zg (Z values) are strictly
+ * increasing and need not be uniform -- the caller's promise, not checked here.  Ray j runs from pa[j] to pb[j]; it is cut at every crossing with a grid line and
+ * at its end points, and only the part inside [xg[0], xg[X-1]] x [zg[0], zg[Z-1]] counts (end points outside are clipped).  A segment of length l inside one
+ * cell gives each of the cell's four corners l times the mean of that corner's bilinear hat function along the segment: the four weights sum to l, the weights
+ * of a ray to its clipped length, and sum(w f) is the exact line integral of the bilinear interpolant of f.  No weight is negative.  A ray of zero length, one
+ * that misses the grid and one with a non-finite coordinate give nothing.  One lane per ray, in the order given; the crossings are merged on the fly from the
+ * grid vectors (kept in LDS, less their first value), never listed or sorted; the walk takes at most K = X + Z + 1 steps whatever the data holds.
+ *   qdas_raypaths_weights    w, ix, iz: DEVICE, 4 x K x J (the 4 corners (ix, iz), (ix+1, iz), (ix, iz+1), (ix+1, iz+1) of a slot together, then the slot, then
+ *                            the ray), w of `dtype`, each aligned to 4 of its elements.  EVERY slot is written: one that holds nothing gets w = 0,
+ *                            ix = iz = -1; indices are 0-based.  Which slot a segment lands in is not part of the contract, the dense sum is.
+ *   qdas_raypaths_integrate  y[j + J f] = sum w map_f[iz zstride + ix xstride] for the F maps (DEVICE, of `dtype`, X Z elements apart), in path order, and
+ *                            -- unless NULL -- len[j] = sum w, the clipped length.  The triplets are never formed.
+ * Sums run in the data's precision, no atomics: results are bit-reproducible.
+ * STREAM.  Both calls are asynchronous on the hipStream_t in the descriptor's `queue` field (as qdas_refocus, and for its reason): no synchronisation, no
+ * allocation, no work space of the library's.  All validation happens on the host before any HIP call: a null descriptor or pointer, X < 2, Z < 2, a point
+ * stride other than 0 | 1 is QDAS_EINVAL; J = 0 (F = 0) is QDAS_OK, nothing is launched, the pointers may be NULL; grid vectors beyond 64 KiB of LDS
+ * (X + Z > 8192 doubles, 16384 singles), more than 65535 maps, more than 2^31 - 1 workgroups of 256 rays or element counts beyond 2^60: QDAS_EUNSUPPORTED. */
+typedef struct qdas_raypaths_desc {
+    uint64_t X, Z, J, F;          /* grid nodes, rays, maps (integrate only)                    */
+    int64_t  xstride, zstride;    /* map / dense-index strides in elements ('ZX': Z, 1; 'XZ': 1, X) */
+    int64_t  pa_stride, pb_stride;/* rays: 1, or 0 = one point for every ray                    */
+    int32_t  dtype, device;       /* QDAS_F32 | QDAS_F64; HIP ordinal, -1 = current             */
+    const void *xg, *zg, *pa, *pb;/* DEVICE: X, Z values; 2 x J (or 2) points, (x, z) pairs     */
+    void    *queue;               /* a hipStream_t                                              */
+} qdas_raypaths_desc;
+uint64_t qdas_raypaths_slots(uint64_t X, uint64_t Z);                       /* X + Z + 1 */
+int qdas_raypaths_weights(const qdas_raypaths_desc *d, void *w, int32_t *ix, int32_t *iz);
+int qdas_raypaths_integrate(const qdas_raypaths_desc *d, const void *maps, void *y, void *len /* may be NULL */);
+
 /* ---- Pair-wise windowed zero-normalized cross-correlation (pwznxcorr.hip): the base-MATLAB branch of the reference's kern/pwznxcorr.m (iflt = false:
  * convn(., w, 'same'), a zero pad at the end of the record, circshift) for every lag in ONE launch.  With h = floor(W / 2), P = max|lags| when `pad` (else 0),
  * Tp = T + P, both records extended by P zeros, K(a)[s] = sum_k w[k] a[s + h - k] for s in [0, Tp) and a = 0 outside [0, Tp) (MATLAB's 'same'):

@@ -63,6 +63,10 @@
  * REFoCUS (src/UltrasoundSystem.m:3735-3762: the decoder Hi applied to the data; building Hi stays in MATLAB, as the reference has it):
  *   y       = qdas_mex('refocus', sizes, x, Hi, t0, fs)
  *         sizes = [T N V M frames]; described at cmd_refocus below.
+ * Straight-ray integrals over a rectilinear grid (kern/wbilerpg.m, and what kern/rayPaths.m / kern/globalAverageC.m make of its triplets):
+ *   [cxy, ixo, iyo] = qdas_mex('wbilerp', gsz, x, y, pa, pb)
+ *   [v, len]        = qdas_mex('rayintegrals', gsz, x, z, pa, pb, maps)
+ *         gsz = [X Y J sa sb] (wbilerp) | [X Z J sa sb F xstride zstride] (rayintegrals); described at cmd_wbilerp / cmd_rayintegrals below.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
  * pass as device pointers and the result is a gpuArray.
  *
@@ -840,13 +844,112 @@ static mxArray *cmd_refocus(int nrhs, const mxArray *prhs[]) {
     return finish(qdas_refocus(&d, x, Hi, y, w->owned, wbytes), host, bytes);
 }
 
+/* the grid and the rays of the two straight-ray commands: gsz = [X Z J sa sb ...]; x, z: real vectors of one class (single | double) with X and Z values,
+ * strictly increasing (the caller's promise, as in the C ABI: wbilerpg.m asserts it before it gets here); pa, pb: 2 x J arrays of that class, a column is
+ * one point (x; z) -- or, with sa / sb = 0, 2 x 1: one point for every ray. */
+static mxClassID ray_args(const char *who, const mxArray *prhs[], qdas_raypaths_desc *d, int *dev) {
+    memset(d, 0, sizeof *d);
+    d->X = (uint64_t)num_at(prhs[0], 0, "gsz"); d->Z = (uint64_t)num_at(prhs[0], 1, "gsz"); d->J = (uint64_t)num_at(prhs[0], 2, "gsz");
+    d->pa_stride = num_at(prhs[0], 3, "gsz") != 0; d->pb_stride = num_at(prhs[0], 4, "gsz") != 0;
+    d->device = -1;
+    const mxClassID cls = mxGetClassID(prhs[1]);
+    if (cls != mxDOUBLE_CLASS && cls != mxSINGLE_CLASS) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "%s: the grid vectors must be single or double.", who);
+    for (int k = 1; k <= 4; ++k)
+        if (mxGetClassID(prhs[k]) != cls || mxIsComplex(prhs[k])) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "%s: grid vectors and end points must be real and of one class.", who);
+    d->dtype = cls == mxDOUBLE_CLASS ? QDAS_F64 : QDAS_F32;
+    if (d->J == 0) return cls;
+    const size_t es = cls == mxDOUBLE_CLASS ? 8 : 4;
+    d->xg = dev_in(prhs[1], (size_t)d->X * es, "x", dev);
+    d->zg = dev_in(prhs[2], (size_t)d->Z * es, "z", dev);
+    d->pa = dev_in(prhs[3], (size_t)(d->pa_stride ? d->J : 1) * 2 * es, "pa", dev);
+    d->pb = dev_in(prhs[4], (size_t)(d->pb_stride ? d->J : 1) * 2 * es, "pb", dev);
+    return cls;
+}
+
+/* a further output of `bytes` bytes the command owns on the device: released with the inputs */
+static void *dev_extra(size_t bytes) {
+    if (g_nda >= QDAS_MEX_MAX_DEVARGS) CFAIL("too many array arguments.");
+    devarg *w = &g_da[g_nda++];
+    memset(w, 0, sizeof *w);
+    if (qdas_device_malloc(&w->owned, bytes, -1)) CFAIL("%s", qdas_last_error());
+    return w->owned;
+}
+
+/* [cxy, ixo, iyo] = qdas_mex('wbilerp', gsz, x, y, pa, pb) -- kern/wbilerpg.m without r: each output is 4 (X + Y + 1) x J; the indices are int32, 1-based and 0
+ * where the slot is empty, as wbilerpg returns them (ixo and iyo come back as host arrays).  Rays outside the grid are clipped without the warning. */
+static void cmd_wbilerp(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
+    if (nrhs != 5) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('wbilerp', gsz, x, y, pa, pb)");
+    qdas_raypaths_desc d;
+    int dev = 0;
+    const mxClassID cls = ray_args("wbilerp", prhs, &d, &dev);
+    const uint64_t K4 = 4 * qdas_raypaths_slots(d.X, d.Z);
+    const mwSize dims[2] = {(mwSize)K4, (mwSize)d.J};
+    if (d.J == 0) {
+        plhs[0] = mxCreateNumericArray(2, dims, cls, mxREAL);
+        for (int k = 1; k < nlhs && k < 3; ++k) plhs[k] = mxCreateNumericArray(2, dims, mxINT32_CLASS, mxREAL);
+        return;
+    }
+    const size_t n = (size_t)(K4 * d.J), bytes = n * (cls == mxDOUBLE_CLASS ? 8 : 4);
+    int32_t *ix = (int32_t *)dev_extra(n * 4), *iz = (int32_t *)dev_extra(n * 4);
+    mxArray *host, *hi[2] = {mxCreateNumericArray(2, dims, mxINT32_CLASS, mxREAL), mxCreateNumericArray(2, dims, mxINT32_CLASS, mxREAL)};
+    void *w = dev_out(2, dims, cls, 0, dev, bytes, &host);
+    int rc = qdas_raypaths_weights(&d, w, ix, iz);
+    rc = fetch_out(rc, host, bytes);
+    if (!rc) rc = qdas_device_copy(mxGetData(hi[0]), ix, n * 4, 1, -1);
+    if (!rc) rc = qdas_device_copy(mxGetData(hi[1]), iz, n * 4, 1, -1);
+    for (int k = 0; k < 2; ++k) {
+        int32_t *v = (int32_t *)mxGetData(hi[k]);
+        for (size_t i = 0; i < n; ++i) v[i] += 1;
+        if (rc || nlhs < k + 2) { mxDestroyArray(hi[k]); hi[k] = NULL; }
+    }
+    plhs[0] = conclude(rc, host);
+    if (hi[0]) plhs[1] = hi[0];
+    if (hi[1]) plhs[2] = hi[1];
+}
+
+/* [v, len] = qdas_mex('rayintegrals', gsz, x, z, pa, pb, maps) -- what globalAverageC.m and the product ``f(:)' * rayPaths(...)`` compute, without the triplets:
+ * v(j, f) = the integral of the bilinear interpolant of map f along ray j (J x F), len(j) the length of the part of the ray inside the grid (a host array).
+ * gsz = [X Z J sa sb F xstride zstride]: maps holds F maps of X Z values of the grid's class; node (ix, iz) of a map is element 1 + ix xstride + iz zstride --
+ * a Z x X array: [Z 1], an X x Z array: [1 X]. */
+static void cmd_rayintegrals(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
+    if (nrhs != 6) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('rayintegrals', gsz, x, z, pa, pb, maps)");
+    qdas_raypaths_desc d;
+    int dev = 0;
+    const uint64_t F = (uint64_t)num_at(prhs[0], 5, "gsz");
+    const int64_t xstride = (int64_t)num_at(prhs[0], 6, "gsz"), zstride = (int64_t)num_at(prhs[0], 7, "gsz");
+    const mxClassID cls = mxGetClassID(prhs[1]);
+    if (!mxIsEmpty(prhs[5]) && (mxGetClassID(prhs[5]) != cls || mxIsComplex(prhs[5]))) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "rayintegrals: the maps must be real and of the grid's class.");
+    ray_args("rayintegrals", prhs, &d, &dev);
+    d.F = F; d.xstride = xstride; d.zstride = zstride;
+    const mwSize dims[2] = {(mwSize)d.J, (mwSize)F}, ldims[2] = {(mwSize)d.J, 1};
+    if (d.J == 0 || F == 0) {
+        release_devargs();
+        plhs[0] = mxCreateNumericArray(2, dims, cls, mxREAL);
+        if (nlhs > 1) plhs[1] = mxCreateNumericArray(2, ldims, cls, mxREAL);
+        return;
+    }
+    if (xstride < 0 || zstride < 0 || (uint64_t)xstride * (d.X - 1) + (uint64_t)zstride * (d.Z - 1) >= d.X * d.Z) CFAIL("rayintegrals: the strides reach outside a map of X Z values.");
+    const size_t es = cls == mxDOUBLE_CLASS ? 8 : 4, bytes = (size_t)(d.J * F) * es;
+    const void *maps = dev_in(prhs[5], (size_t)(d.X * d.Z * F) * es, "maps", &dev);
+    void *len = dev_extra((size_t)d.J * es);
+    mxArray *host, *hl = mxCreateNumericArray(2, ldims, cls, mxREAL);
+    void *y = dev_out(2, dims, cls, 0, dev, bytes, &host);
+    int rc = qdas_raypaths_integrate(&d, maps, y, len);
+    rc = fetch_out(rc, host, bytes);
+    if (!rc) rc = qdas_device_copy(mxGetData(hl), len, (size_t)d.J * es, 1, -1);
+    if (rc || nlhs < 2) { mxDestroyArray(hl); hl = NULL; }
+    plhs[0] = conclude(rc, host);
+    if (hl) plhs[1] = hl;
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
 #ifdef QDAS_MEX_GPU
     mxInitGPU();
 #endif
     char cmd[32] = "";
     if (nrhs >= 1 && mxIsChar(prhs[0]) && mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unreadable command.");
-    if (nlhs > (strcmp(cmd, "pcf") ? 1 : 2)) mexErrMsgIdAndTxt("QUPS:das_spec:nargout", "qdas_mex returns at most one output ('pcf': two).");
+    if (nlhs > (!strcmp(cmd, "wbilerp") ? 3 : (!strcmp(cmd, "pcf") || !strcmp(cmd, "rayintegrals")) ? 2 : 1))
+        mexErrMsgIdAndTxt("QUPS:das_spec:nargout", "qdas_mex returns at most one output ('pcf', 'rayintegrals': two; 'wbilerp': three).");
     if (nrhs >= 1 && mxIsChar(prhs[0])) {
         if (!strcmp(cmd, "create")) {
             const int slot = create_plan(nrhs - 1, prhs + 1);
@@ -887,6 +990,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "adjoint")) { plhs[0] = cmd_adjoint(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "migration")) { plhs[0] = cmd_migration(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "refocus")) { plhs[0] = cmd_refocus(nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "wbilerp")) { cmd_wbilerp(nlhs, plhs, nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "rayintegrals")) { cmd_rayintegrals(nlhs, plhs, nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();
         } else mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unknown command '%s'.", cmd);

@@ -39,6 +39,7 @@ SYMBOLS = (
     "qdas_das_lut", "qdas_das_lut_last_kernel", "qdas_wsinterpd", "qdas_shift_sum", "qdas_greens", "qdas_convd", "qdas_convd_len", "qdas_permute3", "qdas_pre_plan_create", "qdas_pre_execute", "qdas_pre_plan_destroy", "qdas_pre_plan_one_pass", "qdas_last_error", "qdas_version", "qdas_device_malloc", "qdas_device_free", "qdas_device_trim", "qdas_device_copy", "qdas_iir", "qdas_device_info", "qdas_kernel_variant_build", "qdas_kernel_variant_prebuilt",
     "qdas_coherence", "qdas_eikonal", "qdas_eikonal_tables", "qdas_eikonal_last_passes", "qdas_eikonal_pass_cap", "qdas_adjoint", "qdas_migration",
     "qdas_pwznxcorr", "qdas_pwznxcorr_time_tile", "qdas_pwznxcorr_lds_bytes", "qdas_refocus", "qdas_refocus_work_bytes",
+    "qdas_raypaths_slots", "qdas_raypaths_weights", "qdas_raypaths_integrate",
 )
 
 
@@ -145,6 +146,13 @@ class RefocusDesc(C.Structure):
                 ("t0", C.c_void_p), ("queue", C.c_void_p)]
 
 
+class RaypathsDesc(C.Structure):
+    _fields_ = [("X", C.c_uint64), ("Z", C.c_uint64), ("J", C.c_uint64), ("F", C.c_uint64),
+                ("xstride", C.c_int64), ("zstride", C.c_int64), ("pa_stride", C.c_int64), ("pb_stride", C.c_int64),
+                ("dtype", C.c_int32), ("device", C.c_int32),
+                ("xg", C.c_void_p), ("zg", C.c_void_p), ("pa", C.c_void_p), ("pb", C.c_void_p), ("queue", C.c_void_p)]
+
+
 class QdasError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libqdas error {code}: {msg}")
@@ -216,6 +224,10 @@ def lib():
     L.qdas_pwznxcorr_lds_bytes.restype = C.c_uint64
     L.qdas_refocus_work_bytes.argtypes = [C.POINTER(RefocusDesc), C.POINTER(C.c_uint64)]
     L.qdas_refocus.argtypes = [C.POINTER(RefocusDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.qdas_raypaths_slots.argtypes = [C.c_uint64, C.c_uint64]
+    L.qdas_raypaths_slots.restype = C.c_uint64
+    L.qdas_raypaths_weights.argtypes = [C.POINTER(RaypathsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qdas_raypaths_integrate.argtypes = [C.POINTER(RaypathsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64
     L.qdas_shift_sum.argtypes = [C.POINTER(ShiftDesc), C.c_void_p, C.c_void_p, C.c_void_p]
