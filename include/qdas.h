@@ -536,6 +536,45 @@ int qdas_eikonal_tables(const qdas_eikonal_desc *desc, const double *T, const do
 int qdas_eikonal_last_passes(void);
 uint32_t qdas_eikonal_pass_cap(uint64_t C1, uint64_t C2);
 
+/* ---- Travel times through a sound-speed VOLUME, and the delay tables sampled from them (eikonal3.hip): what the reference's bfEikonal computes when the
+ * grid has three non-singleton dimensions -- msfm3d with two arguments (first order, six neighbours) and griddedInterpolant({g1, g2, g3}, T, 'cubic', 'none')
+ * (src/UltrasoundSystem.m:4251-4321).  The 2-D entries' contract above holds with a third coordinate; what differs is stated here.
+ * c: DEVICE C1 x C2 x C3 doubles, C1 fastest (a MATLAB array as it lies in memory); c / dp is msfm's F in cells per second.  src: HOST 3 x npts doubles, one
+ * (first, second, third) grid coordinate per point in the index base `base`, floored to a node; source set k owns the points set_begin[k] ..
+ * set_begin[k+1]-1 (NULL: one point per set, npts == K).  T: DEVICE C1 x C2 x C3 x K doubles, seconds (0 at the source nodes).
+ * qdas_eikonal3 solves all K sets with the same launches, in double precision: tiles of 8 x 8 x 8 nodes, worked off an ACTIVE LIST of (set, tile) pairs, one
+ * launch per pass, to the FIXED POINT of the classical first-order upwind update (a pass that enlists nothing) -- the numbers heap fast marching with
+ * msfm3d's rule produces, to rounding.  No floating-point atomics.
+ * STREAM.  The hipStream_t travels in the descriptor's `queue` field (as qdas_refocus, and for its reason).  qdas_eikonal3 WAITS for that stream: the host
+ * reads the list lengths back every few passes and ends the iteration.  qdas_eikonal3_tables is one launch on `queue`, no synchronisation.
+ * WORK SPACE.  The caller provides it: DEVICE memory of at least qdas_eikonal3_work_bytes(desc) bytes (the same C1, C2, C3, K, npts), aligned to 16 bytes;
+ * the library's per-stream arenas are not used and nothing the work space held before the call is read.  On return its first 8 bytes hold, as a uint64, the
+ * number of tile visits of the solve (the sum of the list lengths over the passes): K tiles passes of them would be a solver without the list.
+ * The number of passes is capped: max_passes, or with 0 qdas_eikonal3_pass_cap(C1, C2, C3) = 8 (C1 + C2 + C3) + 64.  Reaching the cap returns QDAS_ENOCONV and
+ * the maps are set to NaN.  *passes (unless NULL) receives the passes taken; it replaces the 2-D entry's thread-local.
+ * All validation happens on the host before any HIP call: a null descriptor or data pointer, dp <= 0, a base other than 0 | 1, npts != K without set_begin, a
+ * set_begin that does not ascend to npts, an empty set, a point outside the grid, a work space that is too small or misaligned are QDAS_EINVAL;
+ * C1 C2 C3 = 0 or K = 0 is QDAS_OK, nothing is launched, no device needed (work_bytes gives 0); K > 65535, 2^24 or more tiles per map, 2^31 or more nodes in
+ * a dimension, I > 2^32 - 256 are QDAS_EUNSUPPORTED.
+ * qdas_eikonal3_tables: tau[i + I k] = map k at pixel i, for I pixels given as DEVICE 3 x I grid coordinates Pi (same base): separable cubic convolution
+ * (Keys, a = -1/2) along dimension 1, then 2, then 3, the 2-D sampler's ghost nodes dimension by dimension in that order, NaN for a pixel outside the grid; a
+ * zero weight reads nothing, so a pixel on a node gets the node's value bit for bit.  tau is the I1 x I2 x I3 x N layout of qdas_das_lut's tables. */
+typedef struct qdas_eikonal3_desc {
+    uint64_t C1, C2, C3;          /* grid nodes, C1 fastest (a MATLAB C1 x C2 x C3 array as it lies in memory) */
+    uint64_t K, npts;             /* source sets = maps; source points in all                                  */
+    const uint64_t *set_begin;    /* host, K + 1 entries, or NULL (one point per set)                          */
+    double   dp;                  /* grid step                                                                  */
+    int32_t  base, device;        /* index base of src / Pi: 0 | 1; HIP ordinal, -1 = current                   */
+    uint32_t max_passes, reserved;/* 0 = qdas_eikonal3_pass_cap(C1, C2, C3)                                     */
+    uint64_t I;                   /* pixels (tables)                                                            */
+    void    *queue;               /* a hipStream_t                                                              */
+} qdas_eikonal3_desc;
+uint32_t qdas_eikonal3_pass_cap(uint64_t C1, uint64_t C2, uint64_t C3);
+int qdas_eikonal3_work_bytes(const qdas_eikonal3_desc *d, uint64_t *bytes);
+int qdas_eikonal3(const qdas_eikonal3_desc *d, const double *c, const double *src /* HOST 3 x npts */, double *T,
+                  void *work, uint64_t work_bytes, uint32_t *passes /* out, may be NULL */);
+int qdas_eikonal3_tables(const qdas_eikonal3_desc *d, const double *T, const double *Pi /* DEVICE 3 x I */, double *tau);
+
 /* ---- Frequency-domain adjoint beamformer (adjoint.hip): the frequency loop of the reference's bfAdjoint (src/UltrasoundSystem.m:3997-4037) as ONE call.
  * For every pixel i and selected frequency f_k, with tau_rx(i,n) = |Pr_n - Pi| cinv(i), tau_tx(i,m) = |Pt_m - Pi| cinv(i):
  *   S[m,v,k] = apod_tx[m,v] exp(-2 pi i f_k del_tx[m,v])

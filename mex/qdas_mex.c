@@ -55,6 +55,9 @@
  *         first: [] (every point is a source of its own: K = P maps) or the K + 1 offsets (0-based, ascending, last = P) that cut src into K source sets --
  *         a cell {s1, s2, ...} of 2 x P_k arrays is passed as src = [s1 s2 ...], first = [0 cumsum(P_k)]; max_passes: [] | 0 = the derived cap.
  *         T is C1 x C2 x K double (seconds).  An empty F or no points: an empty T, nothing is launched.
+ *   T       = qdas_mex('msfm3d', csz, F, src, first, max_passes)
+ *         the same through a VOLUME (kern/msfm.m for size(F, 3) > 1: msfm3d, first order, six neighbours): csz = [C1 C2 C3]; F: C1 x C2 x C3 double; src: 3 x P
+ *         double; T is C1 x C2 x C3 x K double.
  * The frequency loop of bfAdjoint (src/UltrasoundSystem.m:3997-4037) as one call:
  *   b       = qdas_mex('adjoint', sizes, xk, f, Pi, Pr, Pt, cinv, del_tx, apod_tx, a_n, a_m, flags)
  *         sizes = [I N M V F], flags = [keep_rx keep_tx]; the arrays are described at cmd_adjoint below.  b is I x [N] x [V] single complex.
@@ -732,6 +735,54 @@ static mxArray *cmd_msfm(int nrhs, const mxArray *prhs[]) {
     return finish(rc, host, bytes);
 }
 
+/* T = qdas_mex('msfm3d', csz, F, src, first, max_passes) -- kern/msfm.m:93-113 for a volume (UseSecond = UseCross = false), one call for every source set */
+static mxArray *cmd_msfm3d(int nrhs, const mxArray *prhs[]) {
+    if (nrhs < 3 || nrhs > 5) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('msfm3d', csz, F, src, first, max_passes)");
+    qdas_eikonal3_desc d;
+    memset(&d, 0, sizeof d);
+    d.C1 = (uint64_t)num_at(prhs[0], 0, "csz"); d.C2 = (uint64_t)num_at(prhs[0], 1, "csz"); d.C3 = (uint64_t)num_at(prhs[0], 2, "csz");
+    d.dp = 1.0; d.base = 1; d.device = -1;
+    const mxArray *sa = prhs[2], *fa = nrhs > 3 ? prhs[3] : NULL;
+    if (!mxIsEmpty(sa) && (mxGetClassID(sa) != mxDOUBLE_CLASS || mxIsComplex(sa) || mxGetNumberOfElements(sa) % 3))
+        mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "msfm3d: SourcePoints must be a real double 3 x P array.");
+    d.npts = (uint64_t)(mxGetNumberOfElements(sa) / 3);
+    const int sets = fa && !mxIsEmpty(fa);
+    d.K = sets ? (uint64_t)mxGetNumberOfElements(fa) - 1 : d.npts;
+    if (nrhs > 4 && !mxIsEmpty(prhs[4])) d.max_passes = (uint32_t)num_at(prhs[4], 0, "max_passes");
+    const uint64_t csz[3] = {d.C1, d.C2, d.C3}, CC = d.C1 * d.C2 * d.C3;
+    const mwSize dims[4] = {(mwSize)d.C1, (mwSize)d.C2, (mwSize)d.C3, (mwSize)d.K};
+    if (CC == 0 || d.K == 0 || d.npts == 0)                            /* empty in, empty out */
+        return mxCreateNumericArray(4, (const mwSize[4]){(mwSize)d.C1, (mwSize)d.C2, (mwSize)d.C3, (mwSize)(CC != 0 ? 0 : d.K)}, mxDOUBLE_CLASS, mxREAL);
+    if (mxGetClassID(prhs[1]) != mxDOUBLE_CLASS || mxIsComplex(prhs[1])) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "msfm3d: the speed map must be real double.");
+    /* the reference's range errors, its texts (kern/msfm.m:96-99) */
+    const double *sp = (const double *)mxGetData(sa);
+    for (uint64_t p = 0; p < 3 * d.npts; ++p) if (!(sp[p] >= 1.0)) mexErrMsgIdAndTxt("QUPS:msfm:sourceRange", "Source points must be >= 1 to be within the field.");
+    for (int dim = 0; dim < 3; ++dim)
+        for (uint64_t p = 0; p < d.npts; ++p)
+            if (sp[3 * p + dim] > (double)csz[dim])
+                mexErrMsgIdAndTxt("QUPS:msfm:sourceRange", "Source points must be <= %llu in dimension %d to be in the field.", (unsigned long long)csz[dim], dim + 1);
+    uint64_t *first = NULL, wbytes = 0;
+    if (sets) {
+        first = (uint64_t *)malloc(sizeof(uint64_t) * (d.K + 1));
+        if (!first) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "out of host memory.");
+        for (uint64_t k = 0; k <= d.K; ++k) first[k] = (uint64_t)num_at(fa, (mwSize)k, "first");
+        d.set_begin = first;
+    }
+    if (qdas_eikonal3_work_bytes(&d, &wbytes)) { free(first); mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "%s", qdas_last_error()); }
+    int dev = 0;
+    const size_t bytes = (size_t)(CC * d.K) * 8;
+    const void *c = dev_in(prhs[1], (size_t)CC * 8, "F", &dev);
+    if (g_nda >= QDAS_MEX_MAX_DEVARGS) { free(first); CFAIL("too many array arguments."); }
+    devarg *w = &g_da[g_nda++];                                         /* the work space: owned, released with the inputs */
+    memset(w, 0, sizeof *w);
+    if (qdas_device_malloc(&w->owned, (size_t)wbytes, -1)) { free(first); CFAIL("%s", qdas_last_error()); }
+    mxArray *host;
+    void *T = dev_out(4, dims, mxDOUBLE_CLASS, 0, dev, bytes, &host);
+    const int rc = qdas_eikonal3(&d, (const double *)c, sp, (double *)T, w->owned, wbytes, NULL);
+    free(first);
+    return finish(rc, host, bytes);
+}
+
 /* b = qdas_mex('adjoint', sizes, xk, f, Pi, Pr, Pt, cinv, del_tx, apod_tx, a_n, a_m, flags) -- the parfor of bfAdjoint (src/UltrasoundSystem.m:3997-4037).
  * xk: N x V x F single complex (the selected bins of the spectrum, a_mn applied), f: F doubles [Hz] (host), Pi / Pr / Pt: 3 x I / N / M single,
  * cinv: 1 or I single, del_tx: M x V double (t0Offset added), apod_tx: M x V single, a_n: I x N single or [], a_m: I x V single or [].
@@ -987,6 +1038,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "slsc") || !strcmp(cmd, "dmas") || !strcmp(cmd, "cohfac") || !strcmp(cmd, "pcf")) { cmd_coherence(cmd, nlhs, plhs, nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "pwznxcorr")) { plhs[0] = cmd_pwznxcorr(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "msfm")) { plhs[0] = cmd_msfm(nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "msfm3d")) { plhs[0] = cmd_msfm3d(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "adjoint")) { plhs[0] = cmd_adjoint(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "migration")) { plhs[0] = cmd_migration(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "refocus")) { plhs[0] = cmd_refocus(nrhs - 1, prhs + 1);

@@ -14,7 +14,7 @@ from . import preproc  # noqa: F401,E402
 from .convd import convd, sosfilt  # noqa: F401,E402
 from .coherence import cohfac, dmas, pcf, slsc  # noqa: F401,E402
 from .correlator import pwznxcorr  # noqa: F401,E402
-from .eikonal import msfm  # noqa: F401,E402
+from .eikonal import msfm, msfm3d  # noqa: F401,E402
 from . import adjoint  # noqa: F401,E402  (the module: adjoint.adjoint is the call, a function of the same name would shadow it)
 from . import migration  # noqa: F401,E402
 from . import refocus  # noqa: F401,E402  (the module: refocus.refocus is the call)
@@ -22,4 +22,4 @@ from .raypaths import globalAverageC, rayPaths, ray_integrals, wbilerpg  # noqa:
 from .ultrasound import ChannelData, Scan, Sequence, Transducer, UltrasoundSystem  # noqa: F401,E402
 
 __all__ = ["das_spec", "DasPlan", "MultiDevicePlan", "DasProblem", "DasError", "build_problem", "parse_options", "das_lut", "sample2sep",
-           "wsinterpd2", "convd", "slsc", "dmas", "cohfac", "pcf", "pwznxcorr", "msfm", "adjoint", "migration", "refocus", "wbilerpg", "ray_integrals", "rayPaths", "globalAverageC", "UltrasoundSystem", "Transducer", "Sequence", "Scan", "ChannelData"]
+           "wsinterpd2", "convd", "slsc", "dmas", "cohfac", "pcf", "pwznxcorr", "msfm", "msfm3d", "adjoint", "migration", "refocus", "wbilerpg", "ray_integrals", "rayPaths", "globalAverageC", "UltrasoundSystem", "Transducer", "Sequence", "Scan", "ChannelData"]

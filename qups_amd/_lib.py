@@ -40,6 +40,7 @@ SYMBOLS = (
     "qdas_coherence", "qdas_eikonal", "qdas_eikonal_tables", "qdas_eikonal_last_passes", "qdas_eikonal_pass_cap", "qdas_adjoint", "qdas_migration",
     "qdas_pwznxcorr", "qdas_pwznxcorr_time_tile", "qdas_pwznxcorr_lds_bytes", "qdas_refocus", "qdas_refocus_work_bytes",
     "qdas_raypaths_slots", "qdas_raypaths_weights", "qdas_raypaths_integrate",
+    "qdas_eikonal3", "qdas_eikonal3_tables", "qdas_eikonal3_work_bytes", "qdas_eikonal3_pass_cap",
 )
 
 
@@ -117,6 +118,12 @@ class EikonalDesc(C.Structure):
     _fields_ = [("C1", C.c_uint64), ("C2", C.c_uint64), ("K", C.c_uint64), ("npts", C.c_uint64), ("set_begin", C.POINTER(C.c_uint64)),
                 ("dp", C.c_double), ("base", C.c_int32), ("device", C.c_int32), ("max_passes", C.c_uint32), ("reserved", C.c_uint32),
                 ("I", C.c_uint64)]
+
+
+class Eikonal3Desc(C.Structure):
+    _fields_ = [("C1", C.c_uint64), ("C2", C.c_uint64), ("C3", C.c_uint64), ("K", C.c_uint64), ("npts", C.c_uint64),
+                ("set_begin", C.POINTER(C.c_uint64)), ("dp", C.c_double), ("base", C.c_int32), ("device", C.c_int32),
+                ("max_passes", C.c_uint32), ("reserved", C.c_uint32), ("I", C.c_uint64), ("queue", C.c_void_p)]
 
 
 class AdjointDesc(C.Structure):
@@ -216,6 +223,11 @@ def lib():
     L.qdas_eikonal_last_passes.argtypes = []
     L.qdas_eikonal_pass_cap.argtypes = [C.c_uint64, C.c_uint64]
     L.qdas_eikonal_pass_cap.restype = C.c_uint32
+    L.qdas_eikonal3_pass_cap.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
+    L.qdas_eikonal3_pass_cap.restype = C.c_uint32
+    L.qdas_eikonal3_work_bytes.argtypes = [C.POINTER(Eikonal3Desc), C.POINTER(C.c_uint64)]
+    L.qdas_eikonal3.argtypes = [C.POINTER(Eikonal3Desc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]
+    L.qdas_eikonal3_tables.argtypes = [C.POINTER(Eikonal3Desc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_adjoint.argtypes = [C.POINTER(AdjointDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_migration.argtypes = [C.POINTER(MigrationDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_pwznxcorr.argtypes = [C.POINTER(PwznxcorrDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]

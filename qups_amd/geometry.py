@@ -34,6 +34,24 @@ def convex_array(numel: int, radius: float, angular_pitch_deg: float, offset=(0.
     return p, n
 
 
+def matrix_array(numd, pitch, offset=(0.0, 0.0, 0.0)):
+    """Positions / normals of a matrix array of ``numd = (Nx, Ny)`` elements (a scalar: square) with ``pitch = (px, py)`` (a scalar: both) in the
+    plane ``z = 0``: element ``ix + Nx iy`` lies at ``(x[ix], y[iy], 0)`` -- x runs fastest.
+
+    reference ``src/TransducerMatrix.m:130-138`` (``x = linspace(-w/2, w/2, numd(1))``, ``y`` likewise with ``numd(end)`` and ``pitch(end)``,
+    ``ndgrid(x, y, 0)`` flattened) and ``:140-147`` (normals ``[0; 0; 1]`` with ``rot = 0``).
+    """
+    nd = np.broadcast_to(np.asarray(numd, int).reshape(-1), (2,)) if np.size(numd) == 1 else np.asarray(numd, int).reshape(2)
+    pt = np.broadcast_to(np.asarray(pitch, float).reshape(-1), (2,)) if np.size(pitch) == 1 else np.asarray(pitch, float).reshape(2)
+    w, h = (nd[0] - 1) * pt[0], (nd[1] - 1) * pt[1]
+    x, y = np.linspace(-w / 2, w / 2, nd[0]), np.linspace(-h / 2, h / 2, nd[1])
+    X, Y = np.meshgrid(x, y, indexing="ij")
+    numel = int(nd[0] * nd[1])
+    p = np.stack([X.ravel(order="F"), Y.ravel(order="F"), np.zeros(numel)]) + np.asarray(offset, float).reshape(3, 1)
+    n = np.stack([np.zeros(numel), np.zeros(numel), np.ones(numel)])
+    return p, n
+
+
 def scan_cartesian(x, z, y=(0.0,)):
     """Pixel positions ``3 x I1 x I2 x I3`` of a Cartesian scan in the reference's default order
     ``'ZXY'`` -- depth z is the FASTEST image axis (reference ``src/ScanCartesian.m:11,126-143``,

@@ -24,7 +24,7 @@ class Transducer:
     normals: np.ndarray
     fc: float = 5e6
     offset: np.ndarray = field(default_factory=lambda: np.zeros(3))
-    kind: str = "Transducer"            # the reference's class of the array: 'TransducerArray' (linear), 'TransducerConvex', or the generic base
+    kind: str = "Transducer"            # the reference's class of the array: 'TransducerArray' (linear), 'TransducerConvex', 'TransducerMatrix', or the generic base
     pitch: float | None = None          # element spacing of a linear array
 
     @property
@@ -38,6 +38,11 @@ class Transducer:
     def linear(numel, pitch, fc=5e6, offset=(0.0, 0.0, 0.0)):          # reference src/TransducerArray.m:95-109
         p, n = G.linear_array(numel, pitch, offset)
         return Transducer(p, n, fc, np.asarray(offset, float), "TransducerArray", float(pitch))
+
+    @staticmethod
+    def matrix(numd, pitch, fc=5e6, offset=(0.0, 0.0, 0.0)):           # reference src/TransducerMatrix.m:130-147
+        p, n = G.matrix_array(numd, pitch, offset)
+        return Transducer(p, n, fc, np.asarray(offset, float), "TransducerMatrix")
 
     @staticmethod
     def convex(numel, radius, angular_pitch_deg, fc=3.7e6, offset=(0.0, 0.0, 0.0)):   # reference src/TransducerConvex.m:85-102
@@ -550,7 +555,8 @@ class UltrasoundSystem:
                   delay_only=False, prec=None, return_delays=False):
         """``[b, tau_rx, tau_tx] = bfEikonal(us, chd, med, cgrd, ...)`` (reference ``src/UltrasoundSystem.m:4204-4331``): delay-and-sum with
         travel times through the sound-speed map ``c``, an array of ``cgrd.size`` (a scalar: homogeneous; there is no ``Medium`` class here).
-        ``cgrd`` defaults to ``us.scan`` and must be a Cartesian scan with one singleton dimension and equal steps in the other two.
+        ``cgrd`` defaults to ``us.scan`` and must be a Cartesian scan with equal steps in its non-singleton dimensions: two of them (``msfm2d``), or
+        three -- a volume, solved by ``qups_amd.eikonal.eikonal3`` (``msfm3d``; with a matrix array that is aberration-corrected volumetric imaging).
 
         One travel-time map per element is solved on the device (``qups_amd.eikonal``; the reference: one ``msfm`` call per element, ``:4295-4308``)
         from the element's position floored to a grid node, sampled at the pixels of ``us.scan`` by cubic convolution (NaN outside ``cgrd``; such
@@ -568,7 +574,9 @@ class UltrasoundSystem:
                 raise DasError("Number of transmits must match number of transmitter elements.")
             if not all(int(x.data.shape[x.order.index("N")]) == self.rx.numel for x in chds):
                 raise DasError("Number of receives must match number of receiver elements.")
-        og, dp, dims, axes, csz = E.scan_grid(cgrd)
+        volume = sum(int(v) > 1 for v in tuple(cgrd.size)) == 3                                     # (:4251, :4261-4267: three non-singleton dimensions -> msfm3d)
+        og, dp, dims, axes, csz = E.scan_grid3(cgrd) if volume else E.scan_grid(cgrd)
+        tables = E.travel_time_tables3 if volume else E.travel_time_tables
         if np.ndim(c) == 0:
             cmap = np.full(csz, float(c))
         else:
@@ -587,8 +595,8 @@ class UltrasoundSystem:
         dev = first.data.device if first is not None and hasattr(first.data, "is_cuda") and first.data.is_cuda else None
         if dev is None and hasattr(c, "is_cuda") and c.is_cuda:
             dev = c.device
-        tau_rx = E.travel_time_tables(cmap, dp, Prc, Pic, Isz, device=dev)
-        tau_tx = tau_rx if reuse else E.travel_time_tables(cmap, dp, Pvc, Pic, Isz, device=dev)
+        tau_rx = tables(cmap, dp, Prc, Pic, Isz, device=dev)
+        tau_tx = tau_rx if reuse else tables(cmap, dp, Pvc, Pic, Isz, device=dev)
         if delay_only:
             b = torch.zeros(tuple(Isz) + (self.rx.numel if keep_rx else 1, self.tx.numel if keep_tx else 1, 0), device=tau_rx.device)   # (:4324)
             return b, tau_rx, tau_tx.unsqueeze(3)
