@@ -699,6 +699,49 @@ uint64_t qdas_raypaths_slots(uint64_t X, uint64_t Z);                       /* X
 int qdas_raypaths_weights(const qdas_raypaths_desc *d, void *w, int32_t *ix, int32_t *iz);
 int qdas_raypaths_integrate(const qdas_raypaths_desc *d, const void *maps, void *y, void *len /* may be NULL */);
 
+/* ---- Scan conversion (scanconvert.hip): the reference's ScanPolar.scanConvert (src/ScanPolar.m:143-201: cart2pol, then interp2 per page, NaN outside) and
+ * ScanSpherical.scanConvert (src/ScanSpherical.m:121-188: cart2sph, then interp3) -- an image on a polar grid, b[R x A x pages], or a volume on a spherical
+ * grid, b[R x A x E x pages], onto the Cartesian axes z[Z], x[X] (and y[Y]): out is Z x X x pages (Z x X x Y x pages), dense, Z fastest ('ZXY').  Pages of a
+ * volume are this library's extension.  The source is read in place through its strides (the view DAS returns; complex samples count as one element).
+ * GEOMETRY is float64 whatever the data; the angle axes a, e are in RADIANS (the Python layer and the gateway take degrees as the reference does and convert
+ * with a * pi / 180).  For output pixel (i, j[, y]) with dz = z[i] - origin[2], dx = x[j] - origin[0], dy = y[.] - origin[1]:
+ *   polar      rho = hypot(dz, dx),                alpha = atan2(dx, dz)                                      (cart2pol(Z - oz, X - ox))
+ *   spherical  rho = sqrt(dx^2 + dy^2 + dz^2),     alpha = atan2(dx, dz),   eps = atan2(dy, hypot(dz, dx))    (cart2sph(Z - oz, X - ox, Y - oy))
+ * The pixel is INSIDE iff r[0] <= rho <= r[R-1] and a[0] <= alpha <= a[A-1] (and e[0] <= eps <= e[E-1]): both ends closed, as interp2; a non-finite coordinate
+ * is outside; there is no angle wrap, because the reference has none.  The range cell is the largest k <= R - 2 with r[k] <= rho and
+ * u = (rho - r[k]) / (r[k+1] - r[k]); the angle cells l (m) and weights v (w) follow the same rule: a point on the last node has the last cell and weight 1.
+ * With u, v, w rounded to the data's real type and the arithmetic in that type (contraction to FMA allowed):
+ *   lo = b[k,l] + u (b[k+1,l] - b[k,l]);   hi = b[k,l+1] + u (b[k+1,l+1] - b[k,l+1]);   out = lo + v (hi - lo)
+ * and for a volume the same in the sheet m + 1, then one lerp along e with w: seven lerps, along r, then a, then e.  OUTSIDE, out = fill (the reference: NaN;
+ * pass the canonical quiet NaN); for complex output the real part is fill and the imaginary part 0 -- this library's decision.  Non-finite samples go through
+ * the lerps by IEEE rules: a NaN corner gives NaN even under a zero weight.
+ * PRE acts on the corner samples BEFORE the lerps -- the reference's scanConvert(scan, mod2db(b)), not mod2db of the result.  QDAS_SC_PRE_NONE: out has
+ * the data's type; QDAS_SC_PRE_ABS: |b|; QDAS_SC_PRE_DB: 20 log10 |b|, and a value below db_floor becomes db_floor (-inf: the reference's behaviour, an exact zero
+ * then gives -inf corners and IEEE results around them; a NaN stays a NaN).  With ABS and DB out is REAL, of the data's precision.
+ * The axes are strictly increasing and need not be uniform (the caller's promise, not checked here: they are device vectors).  A workgroup keeps r, a, e in LDS
+ * and finds out for itself whether an axis has a constant pitch (every node within a quarter of it of its place): then the cell is guessed in O(1) and corrected
+ * against the nodes, otherwise it is bisected (QDAS_SCANCONVERT_BISECT=1 in the environment, read per call: always; tests).  Either way the cell is the one named
+ * above on the actual vector.  One lane per output z, looping over the pages; every output element is written exactly once, no atomics: results are bit-reproducible.
+ * STREAM.  The call is asynchronous on the hipStream_t in the descriptor's `queue` field (as qdas_refocus, and for its reason): no synchronisation, no
+ * allocation, no work space of the library's.  All validation happens on the host before any HIP call: a null descriptor, R < 2, A < 2, E = 1, E = 0 with
+ * Y != 0, E >= 2 with Y = 0, an unknown dtype / pre, cplx other than 0 | 1, a non-finite origin, a NaN db_floor, and -- for a call that has work -- a null
+ * pointer is QDAS_EINVAL; Z X max(Y, 1) P = 0 is QDAS_OK, nothing is launched, the pointers may be NULL; R + A + E > 8192 (source axes beyond 64 KiB of LDS),
+ * more than 2^31 - 1 workgroups (256 values of z each) or element counts beyond 2^60: QDAS_EUNSUPPORTED.  Half-precision images are not built. */
+#define QDAS_SC_PRE_NONE 0
+#define QDAS_SC_PRE_ABS  1
+#define QDAS_SC_PRE_DB   2
+typedef struct qdas_scanconvert_desc {
+    uint64_t R, A, E;            /* source nodes; E = 0: polar, E >= 2: spherical            */
+    uint64_t Z, X, Y;            /* output nodes; polar: Y = 0 (there is no y axis)           */
+    uint64_t P;                  /* pages                                                      */
+    int64_t  sr, sa, se, sp;     /* SOURCE strides in elements (the DAS view is read in place) */
+    int32_t  dtype, cplx, pre, device;   /* QDAS_F32 | QDAS_F64; 0 | 1; QDAS_SC_PRE_*; -1 = current */
+    double   origin[3], fill, db_floor;
+    const double *r, *a, *e, *x, *y, *z; /* DEVICE; angles in radians, strictly increasing: the caller's promise */
+    void    *queue;              /* a hipStream_t                                              */
+} qdas_scanconvert_desc;
+int qdas_scanconvert(const qdas_scanconvert_desc *d, const void *b, void *out);  /* out: dense, Z fastest, then X, [Y], pages */
+
 /* ---- Pair-wise windowed zero-normalized cross-correlation (pwznxcorr.hip): the base-MATLAB branch of the reference's kern/pwznxcorr.m (iflt = false:
  * convn(., w, 'same'), a zero pad at the end of the record, circshift) for every lag in ONE launch.  With h = floor(W / 2), P = max|lags| when `pad` (else 0),
  * Tp = T + P, both records extended by P zeros, K(a)[s] = sum_k w[k] a[s + h - k] for s in [0, Tp) and a = 0 outside [0, Tp) (MATLAB's 'same'):

@@ -70,6 +70,9 @@
  *   [cxy, ixo, iyo] = qdas_mex('wbilerp', gsz, x, y, pa, pb)
  *   [v, len]        = qdas_mex('rayintegrals', gsz, x, z, pa, pb, maps)
  *         gsz = [X Y J sa sb] (wbilerp) | [X Z J sa sb F xstride zstride] (rayintegrals); described at cmd_wbilerp / cmd_rayintegrals below.
+ * Scan conversion (src/ScanPolar.m:143-201, src/ScanSpherical.m:121-188; e = [] for a polar scan; angles in degrees):
+ *   bc      = qdas_mex('scanconvert', b, r, a, e, origin, x, y, z, opts)
+ *         opts = [] | [pre db_floor fill] | a struct with those fields; described at cmd_scanconvert below.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
  * pass as device pointers and the result is a gpuArray.
  *
@@ -88,6 +91,7 @@
  * device pointers (QDAS_MEM_DEVICE, mxGPUArray API) and y is returned as a gpuArray: no gather() of the 1.5 GB frame.  A plan is
  * created for ONE memory kind (that of Pi); 'execute' refuses an x of the other kind.
  */
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -993,6 +997,82 @@ static void cmd_rayintegrals(int nlhs, mxArray *plhs[], int nrhs, const mxArray 
     if (hl) plhs[1] = hl;
 }
 
+/* an axis of the scan conversion: a real host vector of any numeric class, as float64 on the device; angles arrive in degrees as the reference keeps them and
+ * become radians here with a * pi / 180 ([] -> NULL, *n = 0) */
+static const double *sc_axis(const mxArray *a, uint64_t *n, int degrees, const char *what) {
+    *n = a ? (uint64_t)mxGetNumberOfElements(a) : 0;
+    if (!*n) return NULL;
+    (void)num_at(a, 0, what);                                                                        /* (raises on a complex or non-numeric array, before anything is held) */
+    double *h = (double *)malloc((size_t)*n * sizeof(double));
+    if (!h) CFAIL("%s: out of memory.", what);
+    for (uint64_t i = 0; i < *n; ++i) h[i] = degrees ? num_at(a, (mwSize)i, what) * 3.14159265358979323846 / 180.0 : num_at(a, (mwSize)i, what);
+    void *d = dev_extra((size_t)*n * sizeof(double));
+    const int rc = qdas_device_copy(d, h, (size_t)*n * sizeof(double), 0, -1);
+    free(h);
+    if (rc) CFAIL("%s", qdas_last_error());
+    return (const double *)d;
+}
+
+/* bc = qdas_mex('scanconvert', b, r, a, e, origin, x, y, z, opts) -- ScanPolar.scanConvert (src/ScanPolar.m:143-201) with e = [] and ScanSpherical.scanConvert
+ * (src/ScanSpherical.m:121-188) otherwise.  b: single | double, real or complex, R x A x pages (R x A x E x pages) as MATLAB holds it (a host array or, in a GPU
+ * build, a gpuArray); r [m], a, e [degrees], origin (3 values), x, y, z [m]: real host vectors, strictly increasing (y is not read for a polar scan and may be
+ * []).  opts: [] | [pre db_floor fill] | a struct with those fields; pre = 0: none, 1: abs, 2: dB (mod2db applied to the samples BEFORE the interpolation),
+ * defaults 0, -Inf, NaN.  bc: Z x X x pages (Z x X x Y x pages) of b's class -- real when pre is 1 or 2 --, fill outside the sector. */
+static mxArray *cmd_scanconvert(int nrhs, const mxArray *prhs[]) {
+    if (nrhs != 9) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('scanconvert', b, r, a, e, origin, x, y, z, opts)");
+    const mxArray *ba = prhs[0], *o = prhs[8];
+    const mxClassID cls = mxGetClassID(ba);
+    if (cls != mxDOUBLE_CLASS && cls != mxSINGLE_CLASS) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "scanconvert: b must be single or double (half-precision images are not built).");
+    qdas_scanconvert_desc d;
+    memset(&d, 0, sizeof d);
+    d.dtype = cls == mxDOUBLE_CLASS ? QDAS_F64 : QDAS_F32;
+    d.cplx = mxIsComplex(ba) ? 1 : 0;
+    d.device = -1;
+    d.pre = QDAS_SC_PRE_NONE; d.db_floor = -INFINITY; d.fill = NAN;
+    if (o && !mxIsEmpty(o)) {
+        const mxArray *f;
+        if (mxIsStruct(o)) {
+            if ((f = mxGetField(o, 0, "pre"))) d.pre = (int32_t)num_at(f, 0, "opts.pre");
+            if ((f = mxGetField(o, 0, "db_floor"))) d.db_floor = num_at(f, 0, "opts.db_floor");
+            if ((f = mxGetField(o, 0, "fill"))) d.fill = num_at(f, 0, "opts.fill");
+        } else {
+            const size_t no = mxGetNumberOfElements(o);
+            d.pre = (int32_t)num_at(o, 0, "opts");
+            if (no > 1) d.db_floor = num_at(o, 1, "opts");
+            if (no > 2) d.fill = num_at(o, 2, "opts");
+        }
+    }
+    for (int k = 0; k < 3; ++k) d.origin[k] = num_at(prhs[4], (mwSize)k, "origin");
+    d.r = sc_axis(prhs[1], &d.R, 0, "r");
+    d.a = sc_axis(prhs[2], &d.A, 1, "a");
+    d.e = sc_axis(prhs[3], &d.E, 1, "e");
+    d.x = sc_axis(prhs[5], &d.X, 0, "x");
+    uint64_t ny = 0;
+    const double *yv = sc_axis(prhs[6], &ny, 0, "y");
+    if (d.E) { d.y = yv; d.Y = ny; }
+    d.z = sc_axis(prhs[7], &d.Z, 0, "z");
+    const uint64_t per = d.R * d.A * (d.E ? d.E : 1), nb = (uint64_t)mxGetNumberOfElements(ba);
+    if (!per || nb % per) CFAIL("scanconvert: b holds %llu samples, not pages of R x A%s = %llu.", (unsigned long long)nb, d.E ? " x E" : "", (unsigned long long)per);
+    d.P = nb / per;
+    d.sr = 1; d.sa = (int64_t)d.R; d.se = d.E ? (int64_t)(d.R * d.A) : 0; d.sp = (int64_t)per;
+    const int ocplx = d.cplx && d.pre == QDAS_SC_PRE_NONE;
+    const mwSize dims[4] = {(mwSize)d.Z, (mwSize)d.X, (mwSize)(d.E ? d.Y : d.P), (mwSize)d.P};
+    const mwSize nd = d.E ? 4 : 3;
+    const uint64_t nout = d.Z * d.X * (d.E ? d.Y : 1) * d.P;
+    const size_t es = (cls == mxDOUBLE_CLASS ? 8 : 4), bytes = (size_t)nout * es * (ocplx ? 2 : 1);
+    if (nout == 0) {
+        const int rc = qdas_scanconvert(&d, NULL, NULL);                                             /* (an empty call is still validated) */
+        if (rc) CFAIL("%s", qdas_last_error());
+        release_devargs();
+        return mxCreateNumericArray(nd, dims, cls, ocplx ? mxCOMPLEX : mxREAL);
+    }
+    int dev = 0;
+    const void *b = dev_in(ba, (size_t)nb * es * (d.cplx ? 2 : 1), "b", &dev);
+    mxArray *host;
+    void *out = dev_out(nd, dims, cls, ocplx, dev, bytes, &host);
+    return finish(qdas_scanconvert(&d, b, out), host, bytes);
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
 #ifdef QDAS_MEX_GPU
     mxInitGPU();
@@ -1044,6 +1124,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "refocus")) { plhs[0] = cmd_refocus(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "wbilerp")) { cmd_wbilerp(nlhs, plhs, nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "rayintegrals")) { cmd_rayintegrals(nlhs, plhs, nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "scanconvert")) { plhs[0] = cmd_scanconvert(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();
         } else mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unknown command '%s'.", cmd);

@@ -19,7 +19,8 @@ from . import adjoint  # noqa: F401,E402  (the module: adjoint.adjoint is the ca
 from . import migration  # noqa: F401,E402
 from . import refocus  # noqa: F401,E402  (the module: refocus.refocus is the call)
 from .raypaths import globalAverageC, rayPaths, ray_integrals, wbilerpg  # noqa: F401,E402
+from .scanconvert import scan_convert, scan_convert3  # noqa: F401,E402
 from .ultrasound import ChannelData, Scan, Sequence, Transducer, UltrasoundSystem  # noqa: F401,E402
 
 __all__ = ["das_spec", "DasPlan", "MultiDevicePlan", "DasProblem", "DasError", "build_problem", "parse_options", "das_lut", "sample2sep",
-           "wsinterpd2", "convd", "slsc", "dmas", "cohfac", "pcf", "pwznxcorr", "msfm", "msfm3d", "adjoint", "migration", "refocus", "wbilerpg", "ray_integrals", "rayPaths", "globalAverageC", "UltrasoundSystem", "Transducer", "Sequence", "Scan", "ChannelData"]
+           "wsinterpd2", "convd", "slsc", "dmas", "cohfac", "pcf", "pwznxcorr", "msfm", "msfm3d", "adjoint", "migration", "refocus", "wbilerpg", "ray_integrals", "rayPaths", "globalAverageC", "scan_convert", "scan_convert3", "UltrasoundSystem", "Transducer", "Sequence", "Scan", "ChannelData"]

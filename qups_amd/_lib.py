@@ -41,6 +41,7 @@ SYMBOLS = (
     "qdas_pwznxcorr", "qdas_pwznxcorr_time_tile", "qdas_pwznxcorr_lds_bytes", "qdas_refocus", "qdas_refocus_work_bytes",
     "qdas_raypaths_slots", "qdas_raypaths_weights", "qdas_raypaths_integrate",
     "qdas_eikonal3", "qdas_eikonal3_tables", "qdas_eikonal3_work_bytes", "qdas_eikonal3_pass_cap",
+    "qdas_scanconvert",
 )
 
 
@@ -160,6 +161,18 @@ class RaypathsDesc(C.Structure):
                 ("xg", C.c_void_p), ("zg", C.c_void_p), ("pa", C.c_void_p), ("pb", C.c_void_p), ("queue", C.c_void_p)]
 
 
+SC_PRE_NONE, SC_PRE_ABS, SC_PRE_DB = 0, 1, 2
+
+
+class ScanconvertDesc(C.Structure):
+    _fields_ = [("R", C.c_uint64), ("A", C.c_uint64), ("E", C.c_uint64), ("Z", C.c_uint64), ("X", C.c_uint64), ("Y", C.c_uint64), ("P", C.c_uint64),
+                ("sr", C.c_int64), ("sa", C.c_int64), ("se", C.c_int64), ("sp", C.c_int64),
+                ("dtype", C.c_int32), ("cplx", C.c_int32), ("pre", C.c_int32), ("device", C.c_int32),
+                ("origin", C.c_double * 3), ("fill", C.c_double), ("db_floor", C.c_double),
+                ("r", C.c_void_p), ("a", C.c_void_p), ("e", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("z", C.c_void_p),
+                ("queue", C.c_void_p)]
+
+
 class QdasError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libqdas error {code}: {msg}")
@@ -240,6 +253,7 @@ def lib():
     L.qdas_raypaths_slots.restype = C.c_uint64
     L.qdas_raypaths_weights.argtypes = [C.POINTER(RaypathsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_raypaths_integrate.argtypes = [C.POINTER(RaypathsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qdas_scanconvert.argtypes = [C.POINTER(ScanconvertDesc), C.c_void_p, C.c_void_p]
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64
     L.qdas_shift_sum.argtypes = [C.POINTER(ShiftDesc), C.c_void_p, C.c_void_p, C.c_void_p]

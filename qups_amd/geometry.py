@@ -70,6 +70,60 @@ def scan_polar(r, a_deg, origin=(0.0, 0.0, 0.0), y=(0.0,)):
     return np.stack([R * np.sin(A) + og[0], Y + og[1], R * np.cos(A) + og[2]])
 
 
+def scan_spherical(r, a_deg, e_deg, origin=(0.0, 0.0, 0.0)):
+    """Pixel positions of a spherical scan, order ``'RAE'``: ``z = r cos e cos a``, ``x = r cos e sin a``, ``y = r sin e`` about ``origin`` -- the
+    reference's ``[Z, X, Y] = sph2cart(deg2rad(A), deg2rad(E), R)`` (``src/ScanSpherical.m:77-93``)."""
+    r, a, e = (np.asarray(v, float).reshape(-1) for v in (r, a_deg, e_deg))
+    R, A, E = np.meshgrid(r, np.deg2rad(a), np.deg2rad(e), indexing="ij")
+    og = np.asarray(origin, float)
+    return np.stack([R * np.cos(E) * np.sin(A) + og[0], R * np.sin(E) + og[1], R * np.cos(E) * np.cos(A) + og[2]])
+
+
+def _enclosing_step(r):
+    """the reference's ``dr`` of an axis (``uniquetol(diff(r), 1e-3)``, ``src/ScanPolar.m:260``) as this package reads it: finite when all ``diff(r)`` agree
+    within ``1e-3 max|diff(r)|``, and then the smallest difference; else NaN (an axis of one node: Inf)"""
+    d = np.diff(np.asarray(r, float).reshape(-1))
+    if d.size == 0:
+        return np.inf
+    return float(d.min()) if d.max() - d.min() <= 1e-3 * np.abs(d).max() else np.nan
+
+
+def _stepped_axis(lo, hi, dr):
+    """``dr * (floor(lo / dr) : ceil(hi / dr))`` (``src/ScanCartesian.m:175-177``).  An axis of zero extent on a multiple of ``dr`` (0, say) is the single
+    value ``dr * floor(lo / dr)``; off a multiple it is, as in the reference, the two multiples around it, so that the axis contains it.  The end indices move
+    out by one where rounding left ``dr * floor(lo / dr)`` above ``lo`` (``dr * ceil(hi / dr)`` below ``hi``): the axis contains ``[lo, hi]``."""
+    k0, k1 = np.floor(lo / dr), np.ceil(hi / dr)
+    k0 -= dr * k0 > lo
+    k1 += dr * k1 < hi
+    return dr * np.arange(k0, k1 + 1)
+
+
+def _enclosing(pos, dr, fallback):
+    lo, hi = pos.reshape(3, -1).min(1), pos.reshape(3, -1).max(1)
+    if np.isfinite(dr) and dr > 0:
+        return tuple(_stepped_axis(lo[k], hi[k], dr) for k in range(3))
+    return tuple(fallback(k, lo[k], hi[k]) for k in range(3))
+
+
+def cartesian_of_polar(r, a_deg, origin=(0.0, 0.0, 0.0), y=(0.0,)):
+    """``(x, y, z)``: the axes of the Cartesian scan that encloses a polar scan, the reference's ``ScanCartesian(scanPolar)`` (``src/ScanPolar.m:203-226``).
+    The bounds are those of all positions, per coordinate.  When the range axis has a step ``dr`` -- all ``diff(r)`` agree within ``1e-3 max|diff(r)|``, this
+    package's reading of ``uniquetol(diff(r), 1e-3)``; ``dr`` is then the smallest difference -- every axis is ``dr * (floor(min / dr) : ceil(max / dr))``
+    and an axis of zero extent on a multiple of ``dr`` the single value ``dr * floor(min / dr)`` (off one: the two multiples around it).  Otherwise the
+    axes keep the reference's default counts: ``linspace(min, max, 161)`` for ``x`` and ``z`` and, for ``y``, the upper bound alone (``linspace(., ., 1)``).
+    The axes contain every position of the source scan."""
+    pos = scan_polar(r, a_deg, origin, y)
+    return _enclosing(pos, _enclosing_step(r), lambda k, lo, hi: np.array([hi]) if k == 1 else np.linspace(lo, hi, 161))
+
+
+def cartesian_of_spherical(r, a_deg, e_deg, origin=(0.0, 0.0, 0.0)):
+    """``(x, y, z)`` that enclose a spherical scan, the reference's ``ScanCartesian(scanSpherical)`` (``src/ScanSpherical.m:190-214``): as
+    :func:`cartesian_of_polar` when the range axis has a step; otherwise the two-point axes ``[min, max]`` the reference leaves behind (it sets ``'x', grd{1}``,
+    the bounds themselves)."""
+    pos = scan_spherical(r, a_deg, e_deg, origin)
+    return _enclosing(pos, _enclosing_step(r), lambda k, lo, hi: np.array([lo, hi]) if hi > lo else np.array([lo]))
+
+
 def sequence_args(seq_type: str, *, tx_pos=None, tx_normals=None, focus=None, tx_offset=(0.0, 0.0, 0.0)):
     """``(Pv, Nv, option_strings)`` exactly as ``UltrasoundSystem.DAS`` derives them from the
     sequence type (reference ``src/UltrasoundSystem.m:3340-3352``):

@@ -104,6 +104,8 @@ class Sequence:
 class Scan:
     """Pixel grid: ``positions()`` is ``3 x I1 x I2 x I3`` (reference ``src/Scan.m:194``)."""
     pos: np.ndarray
+    # the axes the positions were made from, when a constructor below made them: {"kind": "cartesian" | "polar" | "spherical", ...}; None for positions alone
+    axes: dict | None = field(default=None, compare=False, repr=False)
 
     @property
     def size(self):
@@ -114,11 +116,42 @@ class Scan:
 
     @staticmethod
     def cartesian(x, z, y=(0.0,)):                   # order 'ZXY' (reference src/ScanCartesian.m:11,126-143)
-        return Scan(G.scan_cartesian(x, z, y))
+        ax = dict(kind="cartesian", **{k: np.asarray(v, float).reshape(-1) for k, v in (("x", x), ("y", y), ("z", z))})
+        return Scan(G.scan_cartesian(x, z, y), ax)
 
     @staticmethod
     def polar(r, a_deg, origin=(0.0, 0.0, 0.0)):     # order 'RAY' (reference src/ScanPolar.m:11,99-115)
-        return Scan(G.scan_polar(r, a_deg, origin))
+        ax = dict(kind="polar", r=np.asarray(r, float).reshape(-1), a=np.asarray(a_deg, float).reshape(-1), origin=np.asarray(origin, float).reshape(3))
+        return Scan(G.scan_polar(r, a_deg, origin), ax)
+
+    @staticmethod
+    def spherical(r, a_deg, e_deg, origin=(0.0, 0.0, 0.0)):     # order 'RAE' (reference src/ScanSpherical.m:11,77-93)
+        ax = dict(kind="spherical", r=np.asarray(r, float).reshape(-1), a=np.asarray(a_deg, float).reshape(-1), e=np.asarray(e_deg, float).reshape(-1),
+                  origin=np.asarray(origin, float).reshape(3))
+        return Scan(G.scan_spherical(r, a_deg, e_deg, origin), ax)
+
+    def scanConvert(self, b, scanC: "Scan | None" = None, **kw):
+        """``(b_cart, scanC) = scanConvert(scan, b)`` / ``scanConvert(scan, b, scanC)`` (reference ``src/ScanPolar.m:143-201``,
+        ``src/ScanSpherical.m:121-188``): the image ``b`` on this polar (spherical) scan -- ``R x A x ...`` (``R x A x E x ...``), what ``DAS`` returns -- on
+        the Cartesian scan ``scanC``, by default the one that encloses this scan (``ScanCartesian(scan)``).  Keywords (``pre``, ``db_floor``, ``fill``,
+        ``check_grid``) go to :func:`qups_amd.scanconvert.scan_convert` / ``scan_convert3``.  Works on scans made by :meth:`polar` / :meth:`spherical`
+        (and a ``scanC`` made by :meth:`cartesian`): positions alone do not tell the data's order."""
+        from . import scanconvert as SC
+        ax = self.axes
+        if ax is None or ax.get("kind") not in ("polar", "spherical"):
+            raise DasError("Data must be in order 'RAY'.")          # (the reference's refusal, src/ScanPolar.m:193: such a scan does not say how b is ordered)
+        given = {}
+        if scanC is not None:
+            if scanC.axes is None or scanC.axes.get("kind") != "cartesian":
+                raise DasError("scanC must be a Cartesian scan made by Scan.cartesian (order 'ZXY').")
+            given = dict(x=scanC.axes["x"], z=scanC.axes["z"])
+        if ax["kind"] == "polar":
+            bc, (x, y, z) = SC.scan_convert(b, ax["r"], ax["a"], ax["origin"], **given, **kw)
+        else:
+            if scanC is not None:
+                given["y"] = scanC.axes["y"]
+            bc, (x, y, z) = SC.scan_convert3(b, ax["r"], ax["a"], ax["e"], ax["origin"], **given, **kw)
+        return bc, (scanC if scanC is not None else Scan.cartesian(x, z, y))
 
 
 @dataclass
