@@ -53,82 +53,6 @@ struct Args {
     int32_t keep_tx, jacobian, accumulate;
 };
 
-// (c, s) of 2 pi * turns, the turns reduced in fp64 first
-__device__ __forceinline__ float2 phasor(double turns) {
-    turns -= rint(turns);
-    float s, c;
-    sincospif(2.0f * (float)turns, &s, &c);
-    return make_float2(c, s);
-}
-__device__ __forceinline__ float2 conjf2(float2 a) { return make_float2(a.x, -a.y); }
-
-// exp(-2 pi i k / N), k < N
-__global__ void __launch_bounds__(256) mig_twiddles(float2 *tw, uint32_t N) {
-    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= N) return;
-    double sn, cs;
-    sincospi(-2.0 * (double)k / (double)N, &sn, &cs);
-    tw[k] = make_float2((float)cs, (float)sn);
-}
-
-// ---- one transform of length N resident in LDS (padded index lds_pad), in place: thread j owns butterfly j of every stage (pre.hip's scheme).
-// The caller has synchronised after filling `buf`; every stage ends with a barrier.
-template <int R, bool BIG>
-__device__ __forceinline__ void lds_stage(float2 *buf, const float2 *__restrict__ tw, const uint32_t N, const uint32_t Ns) {
-    constexpr int ITER = (BIG && R <= 8) ? 2 : 1;
-    const uint32_t NR = N / R;
-    float2 v[ITER][R];
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-        const uint32_t j = threadIdx.x + it * blockDim.x;
-        if (j < NR) {
-            const uint32_t k = j % Ns;
-#pragma unroll
-            for (int t = 0; t < R; ++t) v[it][t] = buf[lds_pad(j + t * NR)];
-            if (Ns > 1) {
-                float2 w[R];
-                w[1] = tw[k * (NR / Ns)];
-#pragma unroll
-                for (int t = 2; t < R; ++t) w[t] = cmulf(w[t / 2], w[t - t / 2]);
-#pragma unroll
-                for (int t = 1; t < R; ++t) v[it][t] = cmulf(v[it][t], w[t]);
-            }
-            dft_small<R>(v[it], tw, NR);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-        const uint32_t j = threadIdx.x + it * blockDim.x;
-        if (j < NR) {
-            const uint32_t k = j % Ns, j0 = (j - k) * R + k;
-#pragma unroll
-            for (int t = 0; t < R; ++t) buf[lds_pad(j0 + t * Ns)] = v[it][t];
-        }
-    }
-    __syncthreads();
-}
-
-template <bool BIG>
-__device__ __forceinline__ void lds_fft(float2 *buf, const float2 *__restrict__ tw, const FftStages &st, const uint32_t N) {
-    uint32_t Ns = 1;
-    for (int s = 0; s < st.n; ++s) {
-        switch (st.r[s]) {
-            case 2: lds_stage<2, BIG>(buf, tw, N, Ns); break;
-            case 3: lds_stage<3, BIG>(buf, tw, N, Ns); break;
-            case 4: lds_stage<4, BIG>(buf, tw, N, Ns); break;
-            case 5: lds_stage<5, BIG>(buf, tw, N, Ns); break;
-            case 7: lds_stage<7, BIG>(buf, tw, N, Ns); break;
-            case 8: lds_stage<8, BIG>(buf, tw, N, Ns); break;
-            case 9: lds_stage<9, BIG>(buf, tw, N, Ns); break;
-            case 11: lds_stage<11, BIG>(buf, tw, N, Ns); break;
-            case 13: lds_stage<13, BIG>(buf, tw, N, Ns); break;
-            default: lds_stage<16, BIG>(buf, tw, N, Ns); break;
-        }
-        Ns *= st.r[s];
-    }
-}
-
 // ---- pass A
 template <bool BIG>
 __global__ void __launch_bounds__(BIG ? 512 : 256) mig_time(const Args a) {
@@ -144,7 +68,7 @@ __global__ void __launch_bounds__(BIG ? 512 : 256) mig_time(const Args a) {
         mig_lds[lds_pad(i)] = v;
     }
     __syncthreads();
-    lds_fft<BIG>(mig_lds, a.twF, a.stF, F);
+    lds_fft<BIG>(mig_lds, a.twF, a.stF, F, FftBlock{});
     const double td = a.t0 + a.tau[n + (uint64_t)a.N * m];
     const uint32_t hF = F / 2;
     float2 *W = a.W + (uint64_t)F * (n + (uint64_t)a.K * ml);
@@ -166,15 +90,7 @@ __device__ __forceinline__ void lat_stage(const float2 *in, float2 *out, const f
         float2 v[R];
 #pragma unroll
         for (int t = 0; t < R; ++t) v[t] = ri[lds_pad(j + t * NR)];
-        if (Ns > 1) {
-            float2 w[R];
-            w[1] = tw[k * (NR / Ns)];
-#pragma unroll
-            for (int t = 2; t < R; ++t) w[t] = cmulf(w[t / 2], w[t - t / 2]);
-#pragma unroll
-            for (int t = 1; t < R; ++t) v[t] = cmulf(v[t], w[t]);
-        }
-        dft_small<R>(v, tw, NR);
+        QDAS_FFT_BUTTERFLY(R, v, tw, k, NR, Ns);
         float2 *ro = out + row * RS;
         const uint32_t j0 = (j - k) * R + k;
 #pragma unroll
@@ -207,18 +123,7 @@ __global__ void __launch_bounds__(256) mig_lateral(const Args a) {
     __syncthreads();
     uint32_t Ns = 1;
     for (int s = 0; s < a.stK.n; ++s) {
-        switch (a.stK.r[s]) {
-            case 2: lat_stage<2>(A, B, a.twK, K, Ns, RS); break;
-            case 3: lat_stage<3>(A, B, a.twK, K, Ns, RS); break;
-            case 4: lat_stage<4>(A, B, a.twK, K, Ns, RS); break;
-            case 5: lat_stage<5>(A, B, a.twK, K, Ns, RS); break;
-            case 7: lat_stage<7>(A, B, a.twK, K, Ns, RS); break;
-            case 8: lat_stage<8>(A, B, a.twK, K, Ns, RS); break;
-            case 9: lat_stage<9>(A, B, a.twK, K, Ns, RS); break;
-            case 11: lat_stage<11>(A, B, a.twK, K, Ns, RS); break;
-            case 13: lat_stage<13>(A, B, a.twK, K, Ns, RS); break;
-            default: lat_stage<16>(A, B, a.twK, K, Ns, RS); break;
-        }
+        fft_radix(a.stK.r[s], [&](auto r) QDAS_FFT_INLINE { lat_stage<decltype(r)::value>(A, B, a.twK, K, Ns, RS); });
         Ns *= a.stK.r[s];
         float2 *t = A; A = B; B = t;
     }
@@ -274,7 +179,7 @@ __global__ void __launch_bounds__(BIG ? 512 : 256) mig_stolt(const Args a) {
     const double kx = (double)((int)k - (int)(a.K / 2)) / (double)a.K / a.pitch;
     const double cs = a.c0 / sqrt(2.0);
     const double aa = kx * cs * (double)F / a.fs;
-    float2 *ybuf = mig_lds + (F + F / 16 + 1);                           // second tile: the resampled spectrum, then its inverse transform
+    float2 *ybuf = mig_lds + fft_lds_points(F);                             // second tile: the resampled spectrum, then its inverse transform
     float2 acc[QMAX];
 #pragma unroll
     for (int q = 0; q < QMAX; ++q) acc[q] = make_float2(0.f, 0.f);
@@ -296,7 +201,7 @@ __global__ void __launch_bounds__(BIG ? 512 : 256) mig_stolt(const Args a) {
             ybuf[lds_pad(j >= hF ? j - hF : j + F - hF)] = conjf2(cmulf(v, phasor(f * a.t0)));     // conjugate: ifft(Y) = conj(fft(conj(Y))) / F
         }
         __syncthreads();
-        lds_fft<BIG>(ybuf, a.twF, a.stF, F);
+        lds_fft<BIG>(ybuf, a.twF, a.stF, F, FftBlock{});
         const double gz = kx * a.gamma[a.m0 + ml] * (a.c0 / 2.0), gz0 = gz * a.t0, gdz = gz / a.fs;     // turns of step 7 at depth sample i: gz0 + i gdz
         const float sc = 1.0f / (float)F;
         float2 *Y = a.P + (uint64_t)a.Fk * (k + (uint64_t)a.K * ml);
@@ -360,8 +265,8 @@ extern "C" int qdas_migration(const qdas_migration_desc *d, const void *x, void 
     if (!fft_factor(d->F, a.stF, thF) || !fft_factor(d->K, a.stK, thK))
         return fail(QDAS_ENOTLDS, "migration: a transform length outside the in-LDS path (products of 2, 3, 5, 7, 11, 13 from 2 to 8192 whose stages fit a workgroup)");
     const uint32_t F = (uint32_t)d->F, K = (uint32_t)d->K;
-    const uint32_t RS = (K + K / 16 + 1) | 1u;
-    const size_t ldsK = sizeof(float2) * 2 * TF * RS, ldsF = sizeof(float2) * (F + F / 16 + 1), ldsC = 2 * ldsF;
+    const uint32_t RS = fft_lds_points(K) | 1u;
+    const size_t ldsK = sizeof(float2) * 2 * TF * RS, ldsF = sizeof(float2) * fft_lds_points(F), ldsC = 2 * ldsF;
     if (ldsK > LAT_LDS_MAX) return fail(QDAS_ENOTLDS, "migration: K outside the in-LDS path (two tiles of 16 x K points exceed the 160 KiB of LDS)");
     if (!x || !b || !d->tau || !d->gamma) return fail(QDAS_EINVAL, "migration: null data pointer");
     DeviceGuard guard(d->device);
@@ -390,9 +295,7 @@ extern "C" int qdas_migration(const qdas_migration_desc *d, const void *x, void 
     const MigFn fnA = big ? (MigFn)mig_time<true> : (MigFn)mig_time<false>;
     const MigFn fnC = big ? stolt_fn<true>(d->flag) : stolt_fn<false>(d->flag);
     hipError_t e = hipSuccess;
-    if (ldsF > 65536) {
-        if ((e = hipFuncSetAttribute((const void *)fnA, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsF)) != hipSuccess) return hip_fail(e);
-        }
+    if (ldsF > 65536 && (e = hipFuncSetAttribute((const void *)fnA, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsF)) != hipSuccess) return hip_fail(e);
     if (ldsC > 65536 && (e = hipFuncSetAttribute((const void *)fnC, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsC)) != hipSuccess) return hip_fail(e);
     if (ldsK > 65536) {
         if ((e = hipFuncSetAttribute((const void *)mig_lateral<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsK)) != hipSuccess) return hip_fail(e);
@@ -403,8 +306,8 @@ extern "C" int qdas_migration(const qdas_migration_desc *d, const void *x, void 
     a.T = (uint32_t)d->T; a.N = (uint32_t)d->N; a.M = M; a.F = F; a.K = K; a.Fk = Fk; a.Nn = Nn; a.RS = RS; a.mper = mper;
     a.slice_stride = slice;
     a.fs = d->fs; a.fmod = d->fmod; a.t0 = d->t0; a.c0 = d->c0; a.pitch = d->pitch; a.keep_tx = d->keep_tx; a.jacobian = d->jacobian;
-    mig_twiddles<<<(F + 255) / 256, 256, 0, s>>>(tw, F);
-    mig_twiddles<<<(K + 255) / 256, 256, 0, s>>>(tw + F, K);
+    fft_twiddles_kernel<<<(F + 255) / 256, 256, 0, s>>>(tw, F);
+    fft_twiddles_kernel<<<(K + 255) / 256, 256, 0, s>>>(tw + F, K);
     const unsigned ftF = (F + TF - 1) / TF, ftD = (Fk + TF - 1) / TF;
     for (uint64_t fr = 0; fr < d->frames; ++fr) {
         a.frame = fr;

@@ -42,110 +42,51 @@ struct HilbertArgs {
     double fd, t0, fs;
 };
 
-// One Stockham stage of radix R (sub-transform length so far: Ns), in place in `buf` through registers.
-//   ING: the stage opens the forward transform -- its points come from the two real traces in HBM
-//   WGT: the stage opens the inverse transform -- its loads apply the analytic weights and the conjugate (ifft(X) = conj(fft(conj(X))) / N)
-//   OUTG: the stage closes the inverse transform -- its results are finished (x, H x) [* phasor] and go to HBM
-template <int R, bool ING, bool WGT, bool OUTG, typename TI, bool BIG>
-static __device__ __forceinline__ void fft_stage(float2 *buf, const HilbertArgs &A, const uint32_t N, const uint32_t Ns, uint64_t k1, bool two) {
-    constexpr int ITER = (BIG && R <= 8) ? 2 : 1;                        // butterflies per thread (the long-record variant doubles up on the light radices)
-    const uint32_t NR = N / R;
-    float2 v[ITER][R];
-    const TI *x1 = (const TI *)A.x + (uint64_t)A.T * k1, *x2 = x1 + A.T;
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-        const uint32_t j = threadIdx.x + it * blockDim.x;
-        if (j < NR) {
-            const uint32_t k = j % Ns;
-#pragma unroll
-            for (int t = 0; t < R; ++t) {
-                const uint32_t idx = j + t * NR;
-                if constexpr (ING) v[it][t] = make_float2(idx < A.T ? (float)x1[idx] : 0.f, (two && idx < A.T) ? (float)x2[idx] : 0.f);
-                else v[it][t] = buf[lds_pad(idx)];
-                if constexpr (WGT) {                                     // w = [1; 2 ...; 1 + mod(N,2); 0 ...]  (src/ChannelData.m:961-963)
-                    const uint32_t h = N / 2;
-                    const float g = idx == 0 ? 1.f : idx < h ? 2.f : idx == h ? (float)(1 + (N & 1)) : 0.f;
-                    v[it][t] = make_float2(v[it][t].x * g, -v[it][t].y * g);
-                }
-            }
-            if (Ns > 1) {                                                // twiddles exp(-2 pi i k t / (Ns R)): one table entry, the rest by products
-                float2 w[R];
-                w[1] = A.tw[k * (NR / Ns)];
-#pragma unroll
-                for (int t = 2; t < R; ++t) w[t] = cmulf(w[t / 2], w[t - t / 2]);
-#pragma unroll
-                for (int t = 1; t < R; ++t) v[it][t] = cmulf(v[it][t], w[t]);
-            }
-            dft_small<R>(v[it], A.tw, NR);
+// What hilbert's transform does at its ends (fft_lds.h fused_stage): one workgroup's pair of real traces x1, x2 (two: the second exists) of T samples.
+// FIXED: the ops of hilbert_fixed_kernel (see the downmix in store)
+template <typename TI, bool FIXED>
+struct HilbertOps {
+    const TI *x1, *x2; float2 *y1, *y2;
+    bool two; uint32_t T, N;
+    double fd, t0, fs;
+    __device__ __forceinline__ HilbertOps(const HilbertArgs &A, uint32_t N_, uint64_t k1, bool two_)
+        : x1((const TI *)A.x + (uint64_t)A.T * k1), x2(x1 + A.T), y1(A.y + (uint64_t)N_ * k1), y2(y1 + N_), two(two_), T(A.T), N(N_), fd(A.fd), t0(A.t0), fs(A.fs) {}
+    // z = x1 + i x2, zero beyond T
+    __device__ __forceinline__ float2 load(uint32_t idx) const { return make_float2(idx < T ? (float)x1[idx] : 0.f, (two && idx < T) ? (float)x2[idx] : 0.f); }
+    // w = [1; 2 ...; 1 + mod(N,2); 0 ...]  (src/ChannelData.m:961-963), conjugated
+    __device__ __forceinline__ float2 weight(uint32_t idx, float2 v) const {
+        const uint32_t h = N / 2;
+        const float g = idx == 0 ? 1.f : idx < h ? 2.f : idx == h ? (float)(1 + (N & 1)) : 0.f;
+        return make_float2(v.x * g, -v.y * g);
+    }
+    // conj(z) / N = (x1 - H x2) + i (x2 + H x1): the finished (x, H x) [* phasor] of both traces
+    __device__ __forceinline__ void store(uint32_t i, float2 z) const {
+        const float sc = 1.0f / (float)N;
+        const float r1 = i < T ? (float)x1[i] : 0.f, r2 = (two && i < T) ? (float)x2[i] : 0.f;
+        float2 v1 = make_float2(r1, -z.y * sc - r2), v2 = make_float2(r2, r1 - z.x * sc);
+        if (fd != 0.0) {
+            const double cyc = fd * (t0 + (double)i / fs);             // cycles; reduced in fp64 before the fp32 sincos
+            const float ph = (float)(cyc - floor(cyc));
+            const float c = __builtin_amdgcn_cosf(ph), sn = -__builtin_amdgcn_sinf(ph);
+            // The rotation with its fused multiply-adds spelled out.  Left to -ffp-contract, which product of a pair is rounded on its own follows the
+            // code around this one, and it came out differently in one place: the second trace's real part rounds x c in the prebuilt lists' kernels
+            // and y sn in the run-time kernel.  Both are kept as they were, to the bit.
+            v1 = make_float2(__builtin_fmaf(v1.x, c, -(v1.y * sn)), __builtin_fmaf(v1.y, c, v1.x * sn));
+            v2 = make_float2(FIXED ? __builtin_fmaf(-v2.y, sn, v2.x * c) : __builtin_fmaf(v2.x, c, -(v2.y * sn)), __builtin_fmaf(v2.y, c, v2.x * sn));
         }
+        y1[i] = v1;
+        if (two) y2[i] = v2;
     }
-    if constexpr (!ING) __syncthreads();                                 // every butterfly has read its points
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-        const uint32_t j = threadIdx.x + it * blockDim.x;
-        if (j < NR) {
-            const uint32_t k = j % Ns, j0 = (j - k) * R + k;
-            if constexpr (!OUTG) {
-#pragma unroll
-                for (int t = 0; t < R; ++t) buf[lds_pad(j0 + t * Ns)] = v[it][t];
-            } else {                                                     // Ns == N / R here: j0 == j, points j + t NR
-                const float sc = 1.0f / (float)N;
-                float2 *y1 = A.y + (uint64_t)N * k1, *y2 = y1 + N;
-#pragma unroll
-                for (int t = 0; t < R; ++t) {
-                    const uint32_t i = j0 + t * Ns;
-                    const float2 z = v[it][t];                           // conj(z) / N = (x1 - H x2) + i (x2 + H x1)
-                    const float r1 = i < A.T ? (float)x1[i] : 0.f, r2 = (two && i < A.T) ? (float)x2[i] : 0.f;
-                    float2 v1 = make_float2(r1, -z.y * sc - r2), v2 = make_float2(r2, r1 - z.x * sc);
-                    if (A.fd != 0.0) {
-                        const double cyc = A.fd * (A.t0 + (double)i / A.fs);   // cycles; reduced in fp64 before the fp32 sincos
-                        const float ph = (float)(cyc - floor(cyc));
-                        const float c = __builtin_amdgcn_cosf(ph), sn = -__builtin_amdgcn_sinf(ph);
-                        v1 = make_float2(v1.x * c - v1.y * sn, v1.x * sn + v1.y * c);
-                        v2 = make_float2(v2.x * c - v2.y * sn, v2.x * sn + v2.y * c);
-                    }
-                    y1[i] = v1;
-                    if (two) y2[i] = v2;
-                }
-            }
-        }
-    }
-    if constexpr (!OUTG) __syncthreads();
-}
-
-template <bool ING, bool WGT, bool OUTG, typename TI, bool BIG>
-static __device__ __forceinline__ void fft_stage_r(int R, float2 *buf, const HilbertArgs &A, uint32_t Ns, uint64_t k1, bool two) {
-    const uint32_t N = A.N;
-    switch (R) {
-        case 2: fft_stage<2, ING, WGT, OUTG, TI, BIG>(buf, A, N, Ns, k1, two); break;
-        case 3: fft_stage<3, ING, WGT, OUTG, TI, BIG>(buf, A, N, Ns, k1, two); break;
-        case 4: fft_stage<4, ING, WGT, OUTG, TI, BIG>(buf, A, N, Ns, k1, two); break;
-        case 5: fft_stage<5, ING, WGT, OUTG, TI, BIG>(buf, A, N, Ns, k1, two); break;
-        case 7: fft_stage<7, ING, WGT, OUTG, TI, BIG>(buf, A, N, Ns, k1, two); break;
-        case 8: fft_stage<8, ING, WGT, OUTG, TI, BIG>(buf, A, N, Ns, k1, two); break;
-        case 9: fft_stage<9, ING, WGT, OUTG, TI, BIG>(buf, A, N, Ns, k1, two); break;
-        case 11: fft_stage<11, ING, WGT, OUTG, TI, BIG>(buf, A, N, Ns, k1, two); break;
-        case 13: fft_stage<13, ING, WGT, OUTG, TI, BIG>(buf, A, N, Ns, k1, two); break;
-        default: fft_stage<16, ING, WGT, OUTG, TI, BIG>(buf, A, N, Ns, k1, two); break;
-    }
-}
+};
 
 // BIG: up to 512 threads, two butterflies per thread on radices <= 8 (records up to 8192 samples); otherwise up to 256 threads
 template <typename TI, bool BIG>
 __global__ void __launch_bounds__(BIG ? 512 : 256) hilbert_lds_kernel(const HilbertArgs A) {
     extern __shared__ float2 pre_lds[];
     const uint64_t k1 = 2ull * blockIdx.x;
-    const bool two = k1 + 1 < A.K;
-    const int n = A.st.n;
-    uint32_t Ns = 1;
-    fft_stage_r<true, false, false, TI, BIG>(A.st.r[0], pre_lds, A, Ns, k1, two);       // forward
-    Ns = A.st.r[0];
-    for (int s = 1; s < n; ++s) { fft_stage_r<false, false, false, TI, BIG>(A.st.r[s], pre_lds, A, Ns, k1, two); Ns *= A.st.r[s]; }
-    if (n == 1) { fft_stage_r<false, true, true, TI, BIG>(A.st.r[0], pre_lds, A, 1, k1, two); return; }
-    fft_stage_r<false, true, false, TI, BIG>(A.st.r[1], pre_lds, A, 1, k1, two);        // weights, inverse: radices 1 .. n-1, then 0
-    Ns = A.st.r[1];
-    for (int s = 2; s < n; ++s) { fft_stage_r<false, false, false, TI, BIG>(A.st.r[s], pre_lds, A, Ns, k1, two); Ns *= A.st.r[s]; }
-    fft_stage_r<false, false, true, TI, BIG>(A.st.r[0], pre_lds, A, Ns, k1, two);
+    const HilbertOps<TI, false> ops(A, A.N, k1, k1 + 1 < A.K);
+    fused_forward<BIG>(pre_lds, A.tw, A.st, A.N, ops);
+    fused_inverse<BIG>(pre_lds, A.tw, A.st, A.N, ops);
 }
 
 // The same transform with the stage list (hence N, every stride and every twiddle step) known at compile time: the lists of the usual record
@@ -155,15 +96,15 @@ __global__ void __launch_bounds__(BIG ? 512 : 256) hilbert_fixed_kernel(const Hi
     extern __shared__ float2 pre_lds[];
     constexpr uint32_t N = (uint32_t)R0 * R1 * R2 * R3;
     const uint64_t k1 = 2ull * blockIdx.x;
-    const bool two = k1 + 1 < A.K;
-    fft_stage<R0, true, false, false, TI, BIG>(pre_lds, A, N, 1, k1, two);
-    fft_stage<R1, false, false, false, TI, BIG>(pre_lds, A, N, R0, k1, two);
-    if constexpr (R2 > 1) fft_stage<R2, false, false, false, TI, BIG>(pre_lds, A, N, R0 * R1, k1, two);
-    if constexpr (R3 > 1) fft_stage<R3, false, false, false, TI, BIG>(pre_lds, A, N, R0 * R1 * R2, k1, two);
-    fft_stage<R1, false, true, false, TI, BIG>(pre_lds, A, N, 1, k1, two);
-    if constexpr (R2 > 1) fft_stage<R2, false, false, false, TI, BIG>(pre_lds, A, N, R1, k1, two);
-    if constexpr (R3 > 1) fft_stage<R3, false, false, false, TI, BIG>(pre_lds, A, N, R1 * R2, k1, two);
-    fft_stage<R0, false, false, true, TI, BIG>(pre_lds, A, N, R1 * R2 * R3, k1, two);
+    const HilbertOps<TI, true> ops(A, N, k1, k1 + 1 < A.K);
+    fused_stage<R0, true, false, false, BIG>(pre_lds, A.tw, N, 1, ops);
+    fused_stage<R1, false, false, false, BIG>(pre_lds, A.tw, N, R0, ops);
+    if constexpr (R2 > 1) fused_stage<R2, false, false, false, BIG>(pre_lds, A.tw, N, R0 * R1, ops);
+    if constexpr (R3 > 1) fused_stage<R3, false, false, false, BIG>(pre_lds, A.tw, N, R0 * R1 * R2, ops);
+    fused_stage<R1, false, true, false, BIG>(pre_lds, A.tw, N, 1, ops);
+    if constexpr (R2 > 1) fused_stage<R2, false, false, false, BIG>(pre_lds, A.tw, N, R1, ops);
+    if constexpr (R3 > 1) fused_stage<R3, false, false, false, BIG>(pre_lds, A.tw, N, R1 * R2, ops);
+    fused_stage<R0, false, false, true, BIG>(pre_lds, A.tw, N, R1 * R2 * R3, ops);
 }
 
 typedef void (*HilbertFn)(const HilbertArgs);
@@ -253,12 +194,13 @@ int pre_create(PrePlan **out, uint64_t T, uint64_t K, uint64_t N, int in_type, d
     if (p->N == 0 || K == 0) { *out = p; return 0; }
     const char *force = getenv("QDAS_PRE_HIPFFT");
     if (!(force && force[0] == '1') && p->N <= 0xffffffffull && T <= 0xffffffffull && fft_factor(p->N, p->st, p->threads)) {
-        std::vector<float2> h(p->N);
+        std::vector<float2> h(p->N);                                     // the host's cos / sin: rounded differently from fft_twiddle's sincospi here and there, and
+                                                                         // hilbert's results carry this table's bits -- it stays
         for (uint64_t k = 0; k < p->N; ++k) {
             const double a = -2.0 * M_PI * (double)k / (double)p->N;
             h[k] = make_float2((float)cos(a), (float)sin(a));
         }
-        const size_t lds_bytes = sizeof(float2) * (p->N + p->N / 16 + 1);
+        const size_t lds_bytes = sizeof(float2) * fft_lds_points(p->N);
         bool ok = hipMalloc(&p->tw, sizeof(float2) * p->N) == hipSuccess &&
                   qdas_internal_upload(p->tw, h.data(), sizeof(float2) * p->N) == (int)hipSuccess;
         if (ok && lds_bytes > 65536) {
@@ -298,7 +240,7 @@ int pre_execute(PrePlan *p, const void *x, void *y, hipStream_t s) {
     if (p->lds) {
         HilbertArgs A{x, (float2 *)y, p->tw, (uint32_t)p->T, (uint32_t)p->N, p->K, p->st, p->fd, p->t0, p->fs};
         const unsigned nb = (unsigned)((p->K + 1) / 2);
-        const size_t lds_bytes = sizeof(float2) * (p->N + p->N / 16 + 1);
+        const size_t lds_bytes = sizeof(float2) * fft_lds_points(p->N);
         const unsigned th = p->threads & 0xffffu;
         const bool big = (p->threads >> 16) != 0;
         if (const FixedList *f = fixed_list(p->st, big)) {
@@ -336,106 +278,47 @@ struct FftConvArgs {
     FftStages st;
 };
 
+// exp(-2 pi i k / N), k < N (declared in fft_lds.h: migration.hip and refocus.hip launch it)
+__global__ void __launch_bounds__(256) fft_twiddles_kernel(float2 *tw, uint32_t N) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= N) return;
+    tw[k] = fft_twiddle(k, N);
+}
+
 __global__ void __launch_bounds__(256) fftconv_tables_kernel(const void *taps, int taps_real, uint32_t ntaps, uint32_t N, float2 *H, float2 *tw) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= N) return;
-    double sn, cs;
-    sincospi(-2.0 * (double)k / (double)N, &sn, &cs);
-    tw[k] = make_float2((float)cs, (float)sn);
+    tw[k] = fft_twiddle(k, N);
     double re = 0.0, im = 0.0;
     for (uint32_t n = 0; n < ntaps; ++n) {
         const double yr = taps_real ? (double)((const float *)taps)[n] : (double)((const float2 *)taps)[n].x;
         const double yi = taps_real ? 0.0 : (double)((const float2 *)taps)[n].y;
+        double sn, cs;
         sincospi(-2.0 * (double)(((uint64_t)k * n) % N) / (double)N, &sn, &cs);
         re += yr * cs - yi * sn; im += yr * sn + yi * cs;
     }
     H[k] = make_float2((float)(re / (double)N), (float)(im / (double)N));
 }
 
-//   ING: opens the forward transform (points from the trace in HBM, zero beyond M);  WGT: opens the inverse one (times H, conjugated);
-//   OUTG: closes it (conjugate back, outputs [off, off + L) to HBM)
-template <int R, bool ING, bool WGT, bool OUTG, bool BIG>
-static __device__ __forceinline__ void fftconv_stage(float2 *buf, const FftConvArgs &A, const uint32_t N, const uint32_t Ns, uint64_t k1) {
-    constexpr int ITER = (BIG && R <= 8) ? 2 : 1;
-    const uint32_t NR = N / R;
-    float2 v[ITER][R];
-    const float2 *x = A.x + (uint64_t)A.M * k1;
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-        const uint32_t j = threadIdx.x + it * blockDim.x;
-        if (j < NR) {
-            const uint32_t k = j % Ns;
-#pragma unroll
-            for (int t = 0; t < R; ++t) {
-                const uint32_t idx = j + t * NR;
-                if constexpr (ING) v[it][t] = idx < A.M ? x[idx] : make_float2(0.f, 0.f);
-                else v[it][t] = buf[lds_pad(idx)];
-                if constexpr (WGT) { const float2 p = cmulf(v[it][t], A.H[idx]); v[it][t] = make_float2(p.x, -p.y); }
-            }
-            if (Ns > 1) {
-                float2 w[R];
-                w[1] = A.tw[k * (NR / Ns)];
-#pragma unroll
-                for (int t = 2; t < R; ++t) w[t] = cmulf(w[t / 2], w[t - t / 2]);
-#pragma unroll
-                for (int t = 1; t < R; ++t) v[it][t] = cmulf(v[it][t], w[t]);
-            }
-            dft_small<R>(v[it], A.tw, NR);
-        }
-    }
-    if constexpr (!ING) __syncthreads();
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-        const uint32_t j = threadIdx.x + it * blockDim.x;
-        if (j < NR) {
-            const uint32_t k = j % Ns, j0 = (j - k) * R + k;
-            if constexpr (!OUTG) {
-#pragma unroll
-                for (int t = 0; t < R; ++t) buf[lds_pad(j0 + t * Ns)] = v[it][t];
-            } else {
-                float2 *z = A.z + (uint64_t)A.L * k1;
-#pragma unroll
-                for (int t = 0; t < R; ++t) {
-                    const uint32_t i = j0 + t * Ns;
-                    if (i >= A.off && i - A.off < A.L) z[i - A.off] = make_float2(v[it][t].x, -v[it][t].y);
-                }
-            }
-        }
-    }
-    if constexpr (!OUTG) __syncthreads();
-}
-
-template <bool ING, bool WGT, bool OUTG, bool BIG>
-static __device__ __forceinline__ void fftconv_stage_r(int R, float2 *buf, const FftConvArgs &A, uint32_t Ns, uint64_t k1) {
-    const uint32_t N = A.N;
-    switch (R) {
-        case 2: fftconv_stage<2, ING, WGT, OUTG, BIG>(buf, A, N, Ns, k1); break;
-        case 3: fftconv_stage<3, ING, WGT, OUTG, BIG>(buf, A, N, Ns, k1); break;
-        case 4: fftconv_stage<4, ING, WGT, OUTG, BIG>(buf, A, N, Ns, k1); break;
-        case 5: fftconv_stage<5, ING, WGT, OUTG, BIG>(buf, A, N, Ns, k1); break;
-        case 7: fftconv_stage<7, ING, WGT, OUTG, BIG>(buf, A, N, Ns, k1); break;
-        case 8: fftconv_stage<8, ING, WGT, OUTG, BIG>(buf, A, N, Ns, k1); break;
-        case 9: fftconv_stage<9, ING, WGT, OUTG, BIG>(buf, A, N, Ns, k1); break;
-        case 11: fftconv_stage<11, ING, WGT, OUTG, BIG>(buf, A, N, Ns, k1); break;
-        case 13: fftconv_stage<13, ING, WGT, OUTG, BIG>(buf, A, N, Ns, k1); break;
-        default: fftconv_stage<16, ING, WGT, OUTG, BIG>(buf, A, N, Ns, k1); break;
-    }
-}
+// What the convolution's transform does at its ends (fft_lds.h fused_stage): one workgroup's trace x of M points, its outputs z[0, L)
+struct FftConvOps {
+    const float2 *x, *H; float2 *z;
+    uint32_t M, off, L;
+    __device__ __forceinline__ FftConvOps(const FftConvArgs &A, uint64_t k1) : x(A.x + (uint64_t)A.M * k1), H(A.H), z(A.z + (uint64_t)A.L * k1), M(A.M), off(A.off), L(A.L) {}
+    // the trace, zero beyond M
+    __device__ __forceinline__ float2 load(uint32_t idx) const { return idx < M ? x[idx] : make_float2(0.f, 0.f); }
+    // times the filter's spectrum, conjugated
+    __device__ __forceinline__ float2 weight(uint32_t idx, float2 v) const { const float2 p = cmulf(v, H[idx]); return make_float2(p.x, -p.y); }
+    // conjugate back, outputs [off, off + L) of the linear convolution
+    __device__ __forceinline__ void store(uint32_t i, float2 v) const { if (i >= off && i - off < L) z[i - off] = make_float2(v.x, -v.y); }
+};
 
 template <bool BIG>
 __global__ void __launch_bounds__(BIG ? 512 : 256) fftconv_lds_kernel(const FftConvArgs A) {
     extern __shared__ float2 pre_lds[];
-    const uint64_t k1 = blockIdx.x;
-    const int n = A.st.n;
-    uint32_t Ns = 1;
-    fftconv_stage_r<true, false, false, BIG>(A.st.r[0], pre_lds, A, Ns, k1);
-    Ns = A.st.r[0];
-    for (int s = 1; s < n; ++s) { fftconv_stage_r<false, false, false, BIG>(A.st.r[s], pre_lds, A, Ns, k1); Ns *= A.st.r[s]; }
-    if (n == 1) { fftconv_stage_r<false, true, true, BIG>(A.st.r[0], pre_lds, A, 1, k1); return; }
-    fftconv_stage_r<false, true, false, BIG>(A.st.r[1], pre_lds, A, 1, k1);
-    Ns = A.st.r[1];
-    for (int s = 2; s < n; ++s) { fftconv_stage_r<false, false, false, BIG>(A.st.r[s], pre_lds, A, Ns, k1); Ns *= A.st.r[s]; }
-    fftconv_stage_r<false, false, true, BIG>(A.st.r[0], pre_lds, A, Ns, k1);
+    const FftConvOps ops(A, blockIdx.x);
+    fused_forward<BIG>(pre_lds, A.tw, A.st, A.N, ops);
+    fused_inverse<BIG>(pre_lds, A.tw, A.st, A.N, ops);
 }
 
 // 0: done (asynchronously on `s`), 1: not this path (no transform length up to 8192 takes M + ntaps - 1 points), 2: HIP error
@@ -458,7 +341,7 @@ int fftconv_launch(const void *x, const void *taps, int taps_real, void *z, uint
     if (!N) return 1;
     const bool big = (threads >> 16) != 0;
     const unsigned th = threads & 0xffffu;
-    const size_t lds_bytes = sizeof(float2) * (N + N / 16 + 1);
+    const size_t lds_bytes = sizeof(float2) * fft_lds_points(N);
     if (lds_bytes > 65536) {
         const void *fn = big ? (const void *)fftconv_lds_kernel<true> : (const void *)fftconv_lds_kernel<false>;
         if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) { (void)hipGetLastError(); return 1; }

@@ -22,12 +22,9 @@
 //   X[(k V + v) C + c]    T x V x C   written by pass 1, read by pass 2
 //   Y[(k M + m) C + c]    T x M x C   written by pass 2, read by pass 3
 // Column fastest, frequency slowest: pass 2 reads one contiguous V x C (and writes one M x C) page per frequency; passes 1 and 3 touch 8 NT bytes
-// per (frequency, row).  NT = 16 (full 128-byte lines) up to T = 1024; the LDS tiles of NT traces (8 (T + T / 16 + 1) bytes each, at most 144 KiB
+// per (frequency, row).  NT = 16 (full 128-byte lines) up to T = 1024; the LDS tiles of NT traces (8 fft_lds_points(T) bytes each, at most 144 KiB
 // together) halve it per doubling of T beyond: 8 at 2048, 4 at 4096, 2 at 8192 -- the neighbouring workgroup writes the other part of the line.
 // Every element of X and Y that is read was written by the same call: the work buffer's previous content never matters.
-//
-// The in-LDS stage driver below (lds_stage / lds_fft) is a second copy of migration.hip's, which keeps its own in its namespace: both are built from
-// fft_lds.h, and migration.hip is not touched by this file.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -60,82 +57,6 @@ struct Args {
     int32_t one_t0;
 };
 
-// (c, s) of 2 pi * turns, the turns reduced in fp64 first
-__device__ __forceinline__ float2 phasor(double turns) {
-    turns -= rint(turns);
-    float s, c;
-    sincospif(2.0f * (float)turns, &s, &c);
-    return make_float2(c, s);
-}
-
-// exp(-2 pi i k / N), k < N
-__global__ void __launch_bounds__(256) rf_twiddles(float2 *tw, uint32_t N) {
-    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= N) return;
-    double sn, cs;
-    sincospi(-2.0 * (double)k / (double)N, &sn, &cs);
-    tw[k] = make_float2((float)cs, (float)sn);
-}
-
-// ---- one transform of length N resident in LDS (padded index lds_pad), in place: thread j of its GROUP of `nth` threads owns butterfly j of every stage.
-// A workgroup holds one or two groups, each on a trace of its own (`active`: the group has one); the barriers are the workgroup's, so every thread comes
-// here the same number of times.  The caller has synchronised after filling `buf`; every stage ends with a barrier.
-template <int R, bool BIG>
-__device__ __forceinline__ void lds_stage(float2 *buf, const float2 *__restrict__ tw, const uint32_t N, const uint32_t Ns, const uint32_t tid, const uint32_t nth, const bool active) {
-    constexpr int ITER = (BIG && R <= 8) ? 2 : 1;
-    const uint32_t NR = N / R;
-    float2 v[ITER][R];
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-        const uint32_t j = tid + it * nth;
-        if (active && j < NR) {
-            const uint32_t k = j % Ns;
-#pragma unroll
-            for (int t = 0; t < R; ++t) v[it][t] = buf[lds_pad(j + t * NR)];
-            if (Ns > 1) {
-                float2 w[R];
-                w[1] = tw[k * (NR / Ns)];
-#pragma unroll
-                for (int t = 2; t < R; ++t) w[t] = cmulf(w[t / 2], w[t - t / 2]);
-#pragma unroll
-                for (int t = 1; t < R; ++t) v[it][t] = cmulf(v[it][t], w[t]);
-            }
-            dft_small<R>(v[it], tw, NR);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-        const uint32_t j = tid + it * nth;
-        if (active && j < NR) {
-            const uint32_t k = j % Ns, j0 = (j - k) * R + k;
-#pragma unroll
-            for (int t = 0; t < R; ++t) buf[lds_pad(j0 + t * Ns)] = v[it][t];
-        }
-    }
-    __syncthreads();
-}
-
-template <bool BIG>
-__device__ __forceinline__ void lds_fft(float2 *buf, const float2 *__restrict__ tw, const FftStages &st, const uint32_t N, const uint32_t tid, const uint32_t nth, const bool active) {
-    uint32_t Ns = 1;
-    for (int s = 0; s < st.n; ++s) {
-        switch (st.r[s]) {
-            case 2: lds_stage<2, BIG>(buf, tw, N, Ns, tid, nth, active); break;
-            case 3: lds_stage<3, BIG>(buf, tw, N, Ns, tid, nth, active); break;
-            case 4: lds_stage<4, BIG>(buf, tw, N, Ns, tid, nth, active); break;
-            case 5: lds_stage<5, BIG>(buf, tw, N, Ns, tid, nth, active); break;
-            case 7: lds_stage<7, BIG>(buf, tw, N, Ns, tid, nth, active); break;
-            case 8: lds_stage<8, BIG>(buf, tw, N, Ns, tid, nth, active); break;
-            case 9: lds_stage<9, BIG>(buf, tw, N, Ns, tid, nth, active); break;
-            case 11: lds_stage<11, BIG>(buf, tw, N, Ns, tid, nth, active); break;
-            case 13: lds_stage<13, BIG>(buf, tw, N, Ns, tid, nth, active); break;
-            default: lds_stage<16, BIG>(buf, tw, N, Ns, tid, nth, active); break;
-        }
-        Ns *= st.r[s];
-    }
-}
-
 // ---- pass 1: x[t, n, v, frame] -> X[k, v, c]
 template <bool BIG>
 __global__ void __launch_bounds__(512) rf_fft(const Args a) {
@@ -154,7 +75,7 @@ __global__ void __launch_bounds__(512) rf_fft(const Args a) {
         __syncthreads();
         uint32_t Tj = T;
         asm volatile("" : "+s"(Tj));                                    // opaque per trace: the stage indices of every radix are not hoisted out of this loop (registers)
-        lds_fft<BIG>(tile, a.tw, a.st, Tj, tid, nth, active);
+        lds_fft<BIG>(tile, a.tw, a.st, Tj, FftGroup{tid, nth, active});
     }
     const double dt = a.one_t0 ? 0.0 : a.t0[v] * (a.fs / (double)T);        // turns per frequency bin
     for (uint32_t idx = threadIdx.x; idx < NT * T; idx += blockDim.x) {
@@ -228,7 +149,7 @@ __global__ void __launch_bounds__(512) rf_ifft(const Args a) {
         float2 *tile = rf_lds + (active ? j : 0) * a.TS;
         uint32_t Tj = T;
         asm volatile("" : "+s"(Tj));                                    // (as in pass 1)
-        lds_fft<BIG>(tile, a.tw, a.st, Tj, tid, nth, active);
+        lds_fft<BIG>(tile, a.tw, a.st, Tj, FftGroup{tid, nth, active});
         if (active) {
             const uint32_t c = c0 + j, n = c % a.N, fr = c / a.N;
             float2 *y = a.y + (uint64_t)T * (n + (uint64_t)a.N * (m + (uint64_t)a.M * fr));
@@ -248,7 +169,7 @@ static int plan(const qdas_refocus_desc *d, Plan &p) {
     if (d->N * d->frames > LIM) return fail(QDAS_EUNSUPPORTED, "refocus: N * frames is at most 2^31 - 256");
     if (d->V > 65535 || d->M > 65535) return fail(QDAS_EUNSUPPORTED, "refocus: at most 65535 pulses and 65535 elements");
     const uint32_t T = (uint32_t)d->T;
-    p.TS = (T + T / 16 + 1) | 1u;
+    p.TS = fft_lds_points(T) | 1u;
     p.NT = 16;
     while (p.NT > 1 && (size_t)p.NT * p.TS * sizeof(float2) > TILES_LDS_MAX) p.NT /= 2;
     const size_t C = (size_t)(d->N * d->frames);
@@ -315,7 +236,7 @@ extern "C" int qdas_refocus(const qdas_refocus_desc *d, const void *x, const voi
         }
     }
     const unsigned gc = (a.C + a.NT - 1) / a.NT;
-    rf_twiddles<<<(a.T + 255) / 256, 256, 0, s>>>(a.tw, a.T);
+    qdas::fft_twiddles_kernel<<<(a.T + 255) / 256, 256, 0, s>>>(a.tw, a.T);
     f1<<<dim3(gc, a.V), nth * ngrp, lds, s>>>(a);
     rf_decode<<<dim3((a.C + CT - 1) / CT, (a.M + MT - 1) / MT, a.T), 256, 0, s>>>(a);
     f3<<<dim3(gc, a.M), nth * ngrp, lds, s>>>(a);

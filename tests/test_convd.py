@@ -243,7 +243,8 @@ def test_channeldata_filter_and_downsample():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("taps_complex", [False, True], ids=["real-taps", "complex-taps"])
-@pytest.mark.parametrize("T,K", [(700, 129), (2816, 129), (1000, 97), (2048, 301), (5000, 500), (90, 200)])
+@pytest.mark.parametrize("T,K", [(700, 129), (2816, 129), (1000, 97), (2048, 301), (5000, 500), (90, 200),
+                                 (150, 131), (180, 107), (200, 101)])      # transform lengths 280 = 7 5 8, 286 = 13 11 2, 308 = 11 7 4
 def test_convd_long_filters_take_the_fft_path(T, K, taps_complex, monkeypatch):
     """complex64 traces, time contiguous, one filter of >= 128 taps (QDAS_CONV_FFT_MIN_TAPS): the FFT convolution with the trace resident in LDS (csrc/pre.hip fftconv_launch)
     -- every shape against numpy's direct sum in float64 and against the direct kernel (QDAS_CONV_FFT_MIN_TAPS switches the path per call)"""

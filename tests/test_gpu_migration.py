@@ -32,6 +32,8 @@ SHAPES = [
     (60, 20, 1, (60, 20)),        # 3 4 5 x 4 5
     (77, 18, 2, (77, 18)),        # 7 11 x 2 9
     (80, 20, 3, (64, 16)),        # both truncated
+    (100, 40, 2, (770, 77)),      # 11 7 5 2, the 512-thread variant below 8192 points x 11 7
+    (120, 50, 1, (1287, 91)),     # 13 11 9 x 13 7
 ]
 BIG = (8192, 8, 1, (8192, 8))     # the 512-thread stage path
 ODD = (34, 12, 2, (34, 12))       # 17 is no radix: compose

@@ -41,6 +41,8 @@ SHAPES = [
     (60, 33, 1, 4, 1),            # V = 1; N crosses a 32-wide tile
     (77, 2, 35, 33, 1),           # radices 7 11; V and M one tile plus a few
     (80, 4, 8, 1, 2),             # M = 1
+    (770, 2, 2, 2, 1),            # radices 11 7 5 2: the 512-thread variant with two thread groups of 256 threads
+    (1287, 2, 2, 2, 1),           # radices 13 11 9
 ]
 BIG = (8192, 2, 3, 4, 1)          # the 512-thread stage path
 ODD = (34, 3, 4, 4, 1)            # 17 is no radix: compose

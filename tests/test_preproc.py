@@ -60,7 +60,9 @@ def test_hilbert_matches_numpy(T, N, dtype, fdown):
                                                (1000, 1820, 3, "f32", 0.0),       # 2^2 5 7 13
                                                (4000, 3645, 2, "f32", 0.0),       # truncation; 3^6 * 5
                                                (300, 8192, 1, "i16", 0.0),        # 16 8 8 8, 1024 threads
-                                               (9, None, 2, "f32", 0.0), (16, None, 3, "f32", 0.0), (512, None, 2, "f32", 0.0)])
+                                               (9, None, 2, "f32", 0.0), (16, None, 3, "f32", 0.0), (512, None, 2, "f32", 0.0),
+                                               (210, None, 3, "f32", 0.0),        # 7 5 3 2
+                                               (1536, None, 2, "i16", 0.0)])      # 3 8 8 8, 256 threads with two butterflies each
 def test_one_pass_hilbert_matches_numpy(T, N, K, dtype, fdown, force_hipfft, monkeypatch):
     """the LDS-resident kernel (two real traces per complex transform, mixed-radix stages LDS to LDS) against the numpy restatement,
     and the hipFFT passes it replaces against the same numbers"""

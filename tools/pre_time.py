@@ -6,7 +6,8 @@ import ctypes as C, numpy as np, torch
 from qups_amd import _lib
 dev = torch.device("cuda:0")
 T, K = 2816, 65536
-for N, typ, name in ((2816, _lib.QDAS_PRE_F32, "fp32 -> N=2816"), (4096, _lib.QDAS_PRE_I16, "int16 -> N=4096 + downmix")):
+for N, typ, name in ((2816, _lib.QDAS_PRE_F32, "fp32 -> N=2816"), (4096, _lib.QDAS_PRE_I16, "int16 -> N=4096 + downmix"),
+                     (3000, _lib.QDAS_PRE_I16, "int16 -> N=3000 + downmix (5 5 5 3 8: the run-time stage list)")):
     x = (torch.randn((K, T), device=dev) * 1000).to(torch.int16 if typ == _lib.QDAS_PRE_I16 else torch.float32)
     y = torch.empty((K, N), dtype=torch.complex64, device=dev)
     d = _lib.PreDesc(T, K, N, typ, 0, 20e6, 0.0, 5e6 if typ == _lib.QDAS_PRE_I16 else 0.0)

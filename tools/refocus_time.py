@@ -85,7 +85,7 @@ def passes(shape, reps):
             return None, f"rocprofv3 exit {r.returncode}, no kernel_stats.csv: {r.stderr[-300:]}"
         out = {}
         for row in csv.DictReader(open(fs[0])):
-            for name in ("rf_twiddles", "rf_fft", "rf_decode", "rf_ifft"):
+            for name in ("fft_twiddles_kernel", "rf_fft", "rf_decode", "rf_ifft"):
                 if name in row["Name"]:
                     out[name] = (int(row["Calls"]), float(row["AverageNs"]) / 1e3)
         return out, ""
