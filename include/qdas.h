@@ -688,7 +688,7 @@ int qdas_refocus(const qdas_refocus_desc *desc, const void *x, const void *Hi, v
  * stride other than 0 | 1 is QDAS_EINVAL; J = 0 (F = 0) is QDAS_OK, nothing is launched, the pointers may be NULL; grid vectors beyond 64 KiB of LDS
  * (X + Z > 8192 doubles, 16384 singles), more than 65535 maps, more than 2^31 - 1 workgroups of 256 rays or element counts beyond 2^60: QDAS_EUNSUPPORTED. */
 typedef struct qdas_raypaths_desc {
-    uint64_t X, Z, J, F;          /* grid nodes, rays, maps (integrate only)                    */
+    uint64_t X, Z, J, F;          /* grid nodes, rays, maps (integrate) | vectors (backproject) */
     int64_t  xstride, zstride;    /* map / dense-index strides in elements ('ZX': Z, 1; 'XZ': 1, X) */
     int64_t  pa_stride, pb_stride;/* rays: 1, or 0 = one point for every ray                    */
     int32_t  dtype, device;       /* QDAS_F32 | QDAS_F64; HIP ordinal, -1 = current             */
@@ -698,6 +698,17 @@ typedef struct qdas_raypaths_desc {
 uint64_t qdas_raypaths_slots(uint64_t X, uint64_t Z);                       /* X + Z + 1 */
 int qdas_raypaths_weights(const qdas_raypaths_desc *d, void *w, int32_t *ix, int32_t *iz);
 int qdas_raypaths_integrate(const qdas_raypaths_desc *d, const void *maps, void *y, void *len /* may be NULL */);
+/* The transposed product -- back-projection onto the grid, MATLAB's w' * r on the matrix rayPaths returns: with w the weights of qdas_raypaths_weights,
+ *   g_f[iz zstride + ix xstride] = sum_j w_j(ix, iz) r[j + J f]     for the F residual vectors r (DEVICE, of `dtype`), the maps g_f X Z elements apart, and
+ *   colsum[iz zstride + ix xstride] = sum_j w_j(ix, iz)             -- unless NULL -- the column sums of the matrix.
+ * A gather: a lane owns a node and asks every ray for its weight (the node's two hat functions are piecewise linear along the ray: at most three pieces), a
+ * wave a tile of 8 x 8 nodes, and the sum runs in ray order in the data's precision -- no atomics, bit-reproducible, whatever the launch geometry.  EVERY
+ * addressed element of every map is stored exactly once (a node no ray reaches gets 0): the caller need not clear.  A ray that gives nothing in the forward
+ * entries gives nothing here and its r[j] is not looked at: a NaN in r[j] reaches exactly the nodes ray j weighs.  The weights agree with those of the forward
+ * entries to rounding, not bit for bit.
+ * F = 0: a non-NULL colsum is the whole job (r and g may be NULL); with colsum NULL too nothing is launched.  J = 0 writes zeros to the F maps and to colsum
+ * (pa, pb and r may be NULL).  Stream, validation and limits as the two calls above (the same grids are taken both ways), F <= 65535. */
+int qdas_raypaths_backproject(const qdas_raypaths_desc *d, const void *r, void *g, void *colsum /* may be NULL */);
 
 /* ---- Scan conversion (scanconvert.hip): the reference's ScanPolar.scanConvert (src/ScanPolar.m:143-201: cart2pol, then interp2 per page, NaN outside) and
  * ScanSpherical.scanConvert (src/ScanSpherical.m:121-188: cart2sph, then interp3) -- an image on a polar grid, b[R x A x pages], or a volume on a spherical

@@ -69,7 +69,9 @@
  * Straight-ray integrals over a rectilinear grid (kern/wbilerpg.m, and what kern/rayPaths.m / kern/globalAverageC.m make of its triplets):
  *   [cxy, ixo, iyo] = qdas_mex('wbilerp', gsz, x, y, pa, pb)
  *   [v, len]        = qdas_mex('rayintegrals', gsz, x, z, pa, pb, maps)
- *         gsz = [X Y J sa sb] (wbilerp) | [X Z J sa sb F xstride zstride] (rayintegrals); described at cmd_wbilerp / cmd_rayintegrals below.
+ *   [g, col]        = qdas_mex('raybackproject', gsz, x, z, pa, pb, r)
+ *         gsz = [X Y J sa sb] (wbilerp) | [X Z J sa sb F xstride zstride] (rayintegrals, raybackproject); described at cmd_wbilerp / cmd_rayintegrals /
+ *         cmd_raybackproject below.
  * Scan conversion (src/ScanPolar.m:143-201, src/ScanSpherical.m:121-188; e = [] for a polar scan; angles in degrees):
  *   bc      = qdas_mex('scanconvert', b, r, a, e, origin, x, y, z, opts)
  *         opts = [] | [pre db_floor fill] | a struct with those fields; described at cmd_scanconvert below.
@@ -997,6 +999,41 @@ static void cmd_rayintegrals(int nlhs, mxArray *plhs[], int nrhs, const mxArray 
     if (hl) plhs[1] = hl;
 }
 
+/* [g, col] = qdas_mex('raybackproject', gsz, x, z, pa, pb, r) -- the product ``w' * r`` with w the matrix kern/rayPaths.m returns, without the triplets:
+ * g(:, f) = sum_j w_j r(j, f), one map of X Z values per column of r (J x F, of the grid's class), and col = sum_j w_j, the matrix's column sums (a host array).
+ * gsz = [X Z J sa sb F xstride zstride] as 'rayintegrals' takes it; node (ix, iz) of a map is element 1 + ix xstride + iz zstride, and because every element
+ * of an output must be written the strides are those of a Z x X array, [Z 1], or of an X x Z array, [1 X].  F = 0 with two outputs computes col alone. */
+static void cmd_raybackproject(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
+    if (nrhs != 6) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('raybackproject', gsz, x, z, pa, pb, r)");
+    qdas_raypaths_desc d;
+    int dev = 0;
+    const uint64_t F = (uint64_t)num_at(prhs[0], 5, "gsz");
+    const int64_t xstride = (int64_t)num_at(prhs[0], 6, "gsz"), zstride = (int64_t)num_at(prhs[0], 7, "gsz");
+    const mxClassID cls = mxGetClassID(prhs[1]);
+    ray_args("raybackproject", prhs, &d, &dev);
+    if (!mxIsEmpty(prhs[5]) && (mxGetClassID(prhs[5]) != cls || mxIsComplex(prhs[5]))) CFAIL("raybackproject: r must be real and of the grid's class.");
+    d.F = F; d.xstride = xstride; d.zstride = zstride;
+    const mwSize dims[2] = {(mwSize)(d.X * d.Z), (mwSize)F}, cdims[2] = {(mwSize)(d.X * d.Z), 1};
+    if (d.J == 0 || (F == 0 && nlhs < 2)) {                                                          /* zeros: nothing to sum */
+        release_devargs();
+        plhs[0] = mxCreateNumericArray(2, dims, cls, mxREAL);
+        if (nlhs > 1) plhs[1] = mxCreateNumericArray(2, cdims, cls, mxREAL);
+        return;
+    }
+    if (!((xstride == 1 && zstride == (int64_t)d.X) || (zstride == 1 && xstride == (int64_t)d.Z))) CFAIL("raybackproject: the strides must be [Z 1] or [1 X]: every element of a map of X Z values is written.");
+    const size_t es = cls == mxDOUBLE_CLASS ? 8 : 4, bytes = (size_t)(d.X * d.Z * F) * es, cbytes_ = (size_t)(d.X * d.Z) * es;
+    const void *r = F ? dev_in(prhs[5], (size_t)(d.J * F) * es, "r", &dev) : NULL;
+    void *col = nlhs > 1 ? dev_extra(cbytes_) : NULL;
+    mxArray *host = NULL, *hc = nlhs > 1 ? mxCreateNumericArray(2, cdims, cls, mxREAL) : NULL;
+    void *g = F ? dev_out(2, dims, cls, 0, dev, bytes, &host) : NULL;
+    int rc = qdas_raypaths_backproject(&d, r, g, col);
+    if (F) rc = fetch_out(rc, host, bytes);
+    if (!rc && hc) rc = qdas_device_copy(mxGetData(hc), col, cbytes_, 1, -1);
+    if (rc && hc) { mxDestroyArray(hc); hc = NULL; }
+    plhs[0] = F ? conclude(rc, host) : conclude(rc, mxCreateNumericArray(2, dims, cls, mxREAL));
+    if (hc) plhs[1] = hc;
+}
+
 /* an axis of the scan conversion: a real host vector of any numeric class, as float64 on the device; angles arrive in degrees as the reference keeps them and
  * become radians here with a * pi / 180 ([] -> NULL, *n = 0) */
 static const double *sc_axis(const mxArray *a, uint64_t *n, int degrees, const char *what) {
@@ -1079,8 +1116,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
 #endif
     char cmd[32] = "";
     if (nrhs >= 1 && mxIsChar(prhs[0]) && mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unreadable command.");
-    if (nlhs > (!strcmp(cmd, "wbilerp") ? 3 : (!strcmp(cmd, "pcf") || !strcmp(cmd, "rayintegrals")) ? 2 : 1))
-        mexErrMsgIdAndTxt("QUPS:das_spec:nargout", "qdas_mex returns at most one output ('pcf', 'rayintegrals': two; 'wbilerp': three).");
+    if (nlhs > (!strcmp(cmd, "wbilerp") ? 3 : (!strcmp(cmd, "pcf") || !strcmp(cmd, "rayintegrals") || !strcmp(cmd, "raybackproject")) ? 2 : 1))
+        mexErrMsgIdAndTxt("QUPS:das_spec:nargout", "qdas_mex returns at most one output ('pcf', 'rayintegrals', 'raybackproject': two; 'wbilerp': three).");
     if (nrhs >= 1 && mxIsChar(prhs[0])) {
         if (!strcmp(cmd, "create")) {
             const int slot = create_plan(nrhs - 1, prhs + 1);
@@ -1124,6 +1161,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "refocus")) { plhs[0] = cmd_refocus(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "wbilerp")) { cmd_wbilerp(nlhs, plhs, nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "rayintegrals")) { cmd_rayintegrals(nlhs, plhs, nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "raybackproject")) { cmd_raybackproject(nlhs, plhs, nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "scanconvert")) { plhs[0] = cmd_scanconvert(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();

@@ -18,9 +18,9 @@ from .eikonal import msfm, msfm3d  # noqa: F401,E402
 from . import adjoint  # noqa: F401,E402  (the module: adjoint.adjoint is the call, a function of the same name would shadow it)
 from . import migration  # noqa: F401,E402
 from . import refocus  # noqa: F401,E402  (the module: refocus.refocus is the call)
-from .raypaths import globalAverageC, rayPaths, ray_integrals, wbilerpg  # noqa: F401,E402
+from .raypaths import globalAverageC, rayPaths, ray_backproject, ray_integrals, ray_sart, wbilerpg  # noqa: F401,E402
 from .scanconvert import scan_convert, scan_convert3  # noqa: F401,E402
 from .ultrasound import ChannelData, Scan, Sequence, Transducer, UltrasoundSystem  # noqa: F401,E402
 
 __all__ = ["das_spec", "DasPlan", "MultiDevicePlan", "DasProblem", "DasError", "build_problem", "parse_options", "das_lut", "sample2sep",
-           "wsinterpd2", "convd", "slsc", "dmas", "cohfac", "pcf", "pwznxcorr", "msfm", "msfm3d", "adjoint", "migration", "refocus", "wbilerpg", "ray_integrals", "rayPaths", "globalAverageC", "scan_convert", "scan_convert3", "UltrasoundSystem", "Transducer", "Sequence", "Scan", "ChannelData"]
+           "wsinterpd2", "convd", "slsc", "dmas", "cohfac", "pcf", "pwznxcorr", "msfm", "msfm3d", "adjoint", "migration", "refocus", "wbilerpg", "ray_integrals", "ray_backproject", "ray_sart", "rayPaths", "globalAverageC", "scan_convert", "scan_convert3", "UltrasoundSystem", "Transducer", "Sequence", "Scan", "ChannelData"]

@@ -39,7 +39,7 @@ SYMBOLS = (
     "qdas_das_lut", "qdas_das_lut_last_kernel", "qdas_wsinterpd", "qdas_shift_sum", "qdas_greens", "qdas_convd", "qdas_convd_len", "qdas_permute3", "qdas_pre_plan_create", "qdas_pre_execute", "qdas_pre_plan_destroy", "qdas_pre_plan_one_pass", "qdas_last_error", "qdas_version", "qdas_device_malloc", "qdas_device_free", "qdas_device_trim", "qdas_device_copy", "qdas_iir", "qdas_device_info", "qdas_kernel_variant_build", "qdas_kernel_variant_prebuilt",
     "qdas_coherence", "qdas_eikonal", "qdas_eikonal_tables", "qdas_eikonal_last_passes", "qdas_eikonal_pass_cap", "qdas_adjoint", "qdas_migration",
     "qdas_pwznxcorr", "qdas_pwznxcorr_time_tile", "qdas_pwznxcorr_lds_bytes", "qdas_refocus", "qdas_refocus_work_bytes",
-    "qdas_raypaths_slots", "qdas_raypaths_weights", "qdas_raypaths_integrate",
+    "qdas_raypaths_slots", "qdas_raypaths_weights", "qdas_raypaths_integrate", "qdas_raypaths_backproject",
     "qdas_eikonal3", "qdas_eikonal3_tables", "qdas_eikonal3_work_bytes", "qdas_eikonal3_pass_cap",
     "qdas_scanconvert",
 )
@@ -253,6 +253,7 @@ def lib():
     L.qdas_raypaths_slots.restype = C.c_uint64
     L.qdas_raypaths_weights.argtypes = [C.POINTER(RaypathsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_raypaths_integrate.argtypes = [C.POINTER(RaypathsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qdas_raypaths_backproject.argtypes = [C.POINTER(RaypathsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_scanconvert.argtypes = [C.POINTER(ScanconvertDesc), C.c_void_p, C.c_void_p]
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64

@@ -8,6 +8,9 @@ to its clipped length.  Rays of zero length, rays that miss the grid and rays wi
 
 * :func:`wbilerpg` -- the triplets ``(w, ix, iz)``, ``4 x (X + Z + 1)`` per ray (``qdas_raypaths_weights``).
 * :func:`ray_integrals` -- ``sum(w map)`` and the clipped length per ray without ever forming a triplet (``qdas_raypaths_integrate``): the fused path.
+* :func:`ray_backproject` -- the transposed product ``sum_j w_j r[j]`` onto the grid (and the column sums), a gather per node: no triplets, no atomics
+  (``qdas_raypaths_backproject``).  MATLAB's ``w' * r`` on the matrix ``rayPaths`` returns.
+* :func:`ray_sart` -- SART on the two operators: arrival times to a slowness map.
 * :func:`rayPaths` -- the sparse system matrix, from the triplets, in chunks.
 * :func:`globalAverageC` -- on :func:`ray_integrals`.
 
@@ -26,7 +29,7 @@ import numpy as np
 from . import _lib
 from .das_spec import DasError
 
-__all__ = ["wbilerpg", "ray_integrals", "rayPaths", "globalAverageC", "slots", "default_bsize"]
+__all__ = ["wbilerpg", "ray_integrals", "ray_backproject", "ray_sart", "rayPaths", "globalAverageC", "slots", "default_bsize"]
 
 
 def _torch():
@@ -249,6 +252,104 @@ def ray_integrals(maps, xg, zg, pa, pb, ord="ZX", check_grid=True):
     ln = torch.empty((J,), dtype=dtype, device=dev)
     _integrate_into(y, ln, m3, xg, zg, a, b, J, sa, sb, dtype, dev, xstride, zstride)
     return (y if had_F else y[0]), ln
+
+
+def _backproject_into(g, col, r2, xg, zg, a, b, J, sa, sb, dtype, dev, xstride, zstride):
+    """``g``: ``F`` contiguous maps or None (then ``col`` is the whole job); ``r2``: ``F x J`` contiguous; ``col``: one map or None"""
+    torch = _torch()
+    d = _desc(xg, zg, a, b, J, sa, sb, dtype, dev, xstride, zstride, F=0 if g is None else g.shape[0])
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().qdas_raypaths_backproject(C.byref(d), None if g is None else C.c_void_p(r2.data_ptr()), None if g is None else C.c_void_p(g.data_ptr()),
+                                                        None if col is None else C.c_void_p(col.data_ptr())))
+
+
+def _residuals(r, who):
+    """the checks of a residual tensor that need no device: float32 or float64, ``J`` or ``F x J``"""
+    torch = _torch()
+    if not isinstance(r, torch.Tensor):
+        raise DasError(f"{who}: r must be a device tensor")
+    _dtype_of(r)
+    if not r.is_floating_point():
+        raise DasError(f"{who}: float32 or float64 values, got {str(r.dtype).replace('torch.', '')}")
+    if r.ndim not in (1, 2):
+        raise DasError(f"{who}: r holds J values (or F x J), got {tuple(r.shape)}")
+    if not r.is_cuda:
+        raise DasError(f"{who}: r must be a device tensor")
+
+
+def ray_backproject(r, xg, zg, pa, pb, ord="ZX", colsum=False, check_grid=True):
+    """``g``, or ``(g, col)`` with ``colsum=True``: ``g[iz, ix] = sum_j w_j(ix, iz) r[j]`` -- the transposed product of :func:`ray_integrals`, the residuals
+    of the rays ``pa[j] -> pb[j]`` spread back over the nodes each ray weighs -- and ``col[iz, ix] = sum_j w_j(ix, iz)``, the column sums of the system matrix.
+    ``r``: a device tensor of ``J`` values, float32 or float64 -- the precision of the whole computation -- or ``F x J``, then ``g`` is ``F`` maps.  A map is
+    ``Z x X`` for ``ord = "ZX"``, ``X x Z`` for ``"XZ"``, contiguous.  ``pa``, ``pb``: ``2 x J`` (x; z), or one point (``2`` / ``2 x 1``) against many.
+    One kernel, a lane per node asking every ray for its weight: no triplets, no atomics (two runs give the same bits), no synchronisation (with host or
+    unchecked grids).  A ray that gives nothing in :func:`ray_integrals` gives nothing here, whatever its ``r[j]`` holds."""
+    torch = _torch()
+    _strides(ord, 2, 2)
+    _residuals(r, "ray_backproject")
+    dev, dtype = r.device, r.dtype
+    xg, zg = _grid(xg, "x", dtype, dev, check_grid), _grid(zg, "z", dtype, dev, check_grid)
+    X, Z = xg.numel(), zg.numel()
+    a, b, J, sa, sb = _pair(pa, pb, dtype, dev)
+    if r.shape[-1] != J:
+        raise DasError(f"ray_backproject: r holds {r.shape[-1]} values per vector for {J} rays")
+    had_F = r.ndim == 2
+    r2 = (r if had_F else r.unsqueeze(0)).contiguous()
+    F = r2.shape[0]
+    shape = (Z, X) if ord == "ZX" else (X, Z)
+    xstride, zstride = (1, X) if ord == "ZX" else (Z, 1)
+    g = torch.empty((F,) + shape, dtype=dtype, device=dev)
+    col = torch.empty(shape, dtype=dtype, device=dev) if colsum else None
+    _backproject_into(g if F else None, col, r2, xg, zg, a, b, J, sa, sb, dtype, dev, xstride, zstride)
+    g = g if had_F else g[0]
+    return (g, col) if colsum else g
+
+
+def ray_sart(t, xg, zg, pa, pb, s0, iters=10, relax=1.0, ord="ZX", check_grid=True):
+    """the slowness map after ``iters`` steps of SART from ``s0``: ``s <- s + relax C A' R (t - A s)`` with ``A`` the straight-ray matrix of the rays
+    ``pa[j] -> pb[j]`` (:func:`ray_integrals`, :func:`ray_backproject`), ``R = 1 / len`` its row sums (the clipped lengths) and ``C = 1 / colsum`` its
+    column sums, both computed once.  A ray of no length inside the grid and a node no ray weighs get the weight 0: the node keeps ``s0``.
+    ``t``: ``J`` arrival times [s for a map in s/m]; ``s0``: a device tensor, ``Z x X`` (``ord = "ZX"``) or ``X x Z``, float32 or float64 -- the precision of
+    the whole computation; it is not modified.  A fixed count of steps, no convergence test, nothing read back: the loop only queues work.
+    ``relax`` in (0, 2), the range in which SART's weighted residual cannot grow."""
+    torch = _torch()
+    if isinstance(iters, bool) or int(iters) != iters or iters < 0:
+        raise DasError(f"ray_sart: iters must be a non-negative integer, got {iters!r}")
+    if not (0 < float(relax) < 2):
+        raise DasError(f"ray_sart: relax must lie in (0, 2), got {relax!r}")
+    _strides(ord, 2, 2)
+    if not isinstance(s0, torch.Tensor):
+        raise DasError("ray_sart: s0 must be a device tensor")
+    _dtype_of(s0)
+    if not s0.is_cuda or s0.dtype not in (torch.float32, torch.float64):
+        _maps(s0, ord, 2, 2)                                                          # (raises: the message names what is wrong)
+    dev, dtype = s0.device, s0.dtype
+    xg, zg = _grid(xg, "x", dtype, dev, check_grid), _grid(zg, "z", dtype, dev, check_grid)
+    X, Z = xg.numel(), zg.numel()
+    if s0.ndim != 2:
+        raise DasError(f"ray_sart: s0 is one 2-D map, got {tuple(s0.shape)}")
+    _maps(s0, ord, X, Z)
+    a, b, J, sa, sb = _pair(pa, pb, dtype, dev)
+    t = _as(t, dtype, dev).reshape(-1)
+    if t.numel() != J:
+        raise DasError(f"ray_sart: t holds {t.numel()} arrival times for {J} rays")
+    s = s0.clone(memory_format=torch.contiguous_format)
+    xstride, zstride = (1, X) if ord == "ZX" else (Z, 1)
+    if J == 0 or iters == 0:
+        return s
+    geo = (xg, zg, a, b, J, sa, sb, dtype, dev, xstride, zstride)
+    y, ln = torch.empty((1, J), dtype=dtype, device=dev), torch.empty((J,), dtype=dtype, device=dev)
+    g, col = torch.empty_like(s).unsqueeze(0), torch.empty_like(s)
+    _integrate_into(y, ln, s.unsqueeze(0), *geo)
+    _backproject_into(None, col, None, *geo)
+    zero = torch.zeros((), dtype=dtype, device=dev)
+    rinv, cinv = torch.where(ln > 0, 1 / ln, zero), torch.where(col > 0, relax / col, zero)
+    for it in range(int(iters)):
+        if it:
+            _integrate_into(y, None, s.unsqueeze(0), *geo)
+        _backproject_into(g, None, torch.where(ln > 0, (t - y[0]) * rinv, zero).unsqueeze(0), *geo)
+        s.addcmul_(g[0], cinv)
+    return s
 
 
 def rayPaths(xg, zg, pj, pa, ord="ZX", method="bilerp", bsize=None, check_grid=True):
