@@ -753,6 +753,47 @@ typedef struct qdas_scanconvert_desc {
 } qdas_scanconvert_desc;
 int qdas_scanconvert(const qdas_scanconvert_desc *d, const void *b, void *out);  /* out: dense, Z fastest, then X, [Y], pages */
 
+/* ---- Demodulation (demod.hip): the reference's recipe for baseband imaging, downmix(chd, fc) -> filter(chd, D) -> downsample(chd, ratio)
+ * (src/ChannelData.m:757-807, :857-888, :1042-1058), in ONE pass over the record.  For x of T samples x C traces (time contiguous, trace c at x + c x_ld), real
+ * taps b[0 .. K-1], an integer ratio R >= 1 and J = ceil(T / R) = qdas_demod_len(T, R):
+ *   out[j + c out_ld] = sum_{k=0}^{K-1} b[k] x[jR - k, c] exp(-2 pi i frac(fc (t0_c + (jR - k) / fs))),   j = 0 .. J-1,
+ * terms with jR - k < 0 omitted (the causal start of `filter`).  The new time axis is t0' = t0 - (K - 1) / 2 / fs, fs' = fs / R -- the caller's bookkeeping;
+ * the phase uses the ORIGINAL t0, as the composition does.  For real x the result carries half the analytic amplitude, exactly as the composition does
+ * (taps 2 b restore it); there is no gain field.  The kernel evaluates
+ *   out[j] = exp(-2 pi i frac(cyc0_c + frac(j step))) sum_k (b[k] exp(+2 pi i frac(k fc_over_fs))) x[jR - k],   fc_over_fs = fc / fs,  step = fc R / fs,
+ * with the three frac() in float64, sincos and the sums in the data's precision (fp32 accumulators for int16 / float32 / complex64 input, fp64 for double
+ * data), one rounding at the store.  cyc0: DEVICE vector of G >= 1 doubles, frac(fc t0) per start time; trace c uses cyc0[(c / gdiv) % G] (gdiv = N, G = M: one
+ * start time per transmit of a T x N x M record; G = 1: one for all).
+ * TYPES.  in_type QDAS_DEMOD_I16 | _F32 | _C64: out is complex64, or with out_half interleaved half pairs (what qdas_DASh takes); b is float32.
+ * QDAS_DEMOD_F64 | _C128: out is complex128, b is float64; out_half is refused.  b: DEVICE vector of K real taps.
+ * A sample no output reads (K < R: indices with (-i) mod R >= K) is never loaded, and no sample is multiplied by a zero coefficient: a NaN at x[i] reaches
+ * exactly the outputs with 0 <= jR - i < K.  Every output element is written exactly once, out_ld padding is not touched, no atomics: bit-reproducible.
+ * STREAM.  Asynchronous on the hipStream_t in the descriptor's `queue` field (as qdas_scanconvert): no synchronisation, no allocation, no work space.
+ * All validation happens on the host before any HIP call: a null descriptor, R = 0, K = 0, x_ld < T, out_ld < J, an unknown in_type, out_half other than
+ * 0 | 1 or with double data, G = 0, gdiv = 0, a non-finite fc_over_fs / step and -- for a call that has work -- a null x, b, out or cyc0: QDAS_EINVAL.
+ * T C = 0: QDAS_OK, nothing is launched, the pointers may be NULL.  LIMITS: K <= QDAS_DEMOD_MAX_K = 1024 taps and R <= QDAS_DEMOD_MAX_R = 4096 (the modulated
+ * taps and the span of one tile live in at most 64 KiB of LDS), C ceil(J / QDAS_DEMOD_TILE) < 2^31 workgroups, T, C, x_ld, out_ld < 2^40: QDAS_EUNSUPPORTED beyond. */
+#define QDAS_DEMOD_I16  0
+#define QDAS_DEMOD_F32  1
+#define QDAS_DEMOD_C64  2
+#define QDAS_DEMOD_F64  3
+#define QDAS_DEMOD_C128 4
+#define QDAS_DEMOD_MAX_K 1024
+#define QDAS_DEMOD_MAX_R 4096
+#define QDAS_DEMOD_TILE  256    /* outputs of one trace per workgroup */
+typedef struct qdas_demod_desc {
+    uint64_t T, C, K, R;         /* samples per trace, traces, taps, decimation ratio           */
+    uint64_t x_ld, out_ld;       /* trace strides in elements (x_ld >= T, out_ld >= J)          */
+    int32_t  in_type, out_half;  /* QDAS_DEMOD_*; 0 | 1                                         */
+    int32_t  device, reserved;   /* HIP ordinal, -1 = current                                   */
+    double   fc_over_fs, step;   /* fc / fs; fc R / fs  (cycles per input / per output sample)  */
+    const double *cyc0;          /* DEVICE, G values of frac(fc t0)                             */
+    uint64_t gdiv, G;            /* trace c uses cyc0[(c / gdiv) % G]                           */
+    void    *queue;              /* a hipStream_t                                               */
+} qdas_demod_desc;
+uint64_t qdas_demod_len(uint64_t T, uint64_t R);   /* J = ceil(T / R); 0 for R = 0 */
+int qdas_demod(const qdas_demod_desc *d, const void *x, const void *b, void *out);
+
 /* ---- Pair-wise windowed zero-normalized cross-correlation (pwznxcorr.hip): the base-MATLAB branch of the reference's kern/pwznxcorr.m (iflt = false:
  * convn(., w, 'same'), a zero pad at the end of the record, circshift) for every lag in ONE launch.  With h = floor(W / 2), P = max|lags| when `pad` (else 0),
  * Tp = T + P, both records extended by P zeros, K(a)[s] = sum_k w[k] a[s + h - k] for s in [0, Tp) and a = 0 outside [0, Tp) (MATLAB's 'same'):

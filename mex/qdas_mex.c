@@ -75,6 +75,8 @@
  * Scan conversion (src/ScanPolar.m:143-201, src/ScanSpherical.m:121-188; e = [] for a polar scan; angles in degrees):
  *   bc      = qdas_mex('scanconvert', b, r, a, e, origin, x, y, z, opts)
  *         opts = [] | [pre db_floor fill] | a struct with those fields; described at cmd_scanconvert below.
+ *   y       = qdas_mex('demod', x, b, [T fc fs ratio gdiv], t0)
+ *         downmix -> filter -> downsample in one pass; described at cmd_demod below.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
  * pass as device pointers and the result is a gpuArray.
  *
@@ -1110,6 +1112,69 @@ static mxArray *cmd_scanconvert(int nrhs, const mxArray *prhs[]) {
     return finish(qdas_scanconvert(&d, b, out), host, bytes);
 }
 
+/* y = qdas_mex('demod', x, b, prm, t0) -- downmix(chd, fc) -> filter(chd, D) -> downsample(chd, ratio) (src/ChannelData.m:757-807, :857-888, :1042-1058) in one
+ * pass (qdas_demod).  x: int16 | single | double (single, double: real or complex), T x C (any trailing dimensions count as traces) as MATLAB holds it: time
+ * fastest (a host array or, in a GPU build, a gpuArray).  b: the real FIR taps, a host vector of any numeric class (converted to the data's precision).
+ * prm = [T fc fs ratio gdiv] (T = size(x, 1); gdiv optional, default 1); t0: one start time, or G of them -- trace c (0-based) starts at t0(1 + mod(floor(c / gdiv), G)), so
+ * gdiv = N, G = M gives one start time per transmit of a T x N x M record.  y: ceil(T / ratio) x C complex single (double for double data); real data give half
+ * the analytic amplitude, as the composition does.  The new time axis, t0 - (numel(b) - 1) / 2 / fs and fs / ratio, is the caller's bookkeeping.  Half output
+ * is not offered here (MATLAB has no half class). */
+static mxArray *cmd_demod(int nrhs, const mxArray *prhs[]) {
+    if (nrhs != 4) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('demod', x, b, prm, t0)");
+    const mxArray *xa = prhs[0];
+    const mxClassID cls = mxGetClassID(xa);
+    const int cplx = mxIsComplex(xa) ? 1 : 0;
+    if ((cls != mxDOUBLE_CLASS && cls != mxSINGLE_CLASS && cls != mxINT16_CLASS) || (cls == mxINT16_CLASS && cplx))
+        mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "demod: x must be int16 (real), single or double.");
+    qdas_demod_desc d;
+    memset(&d, 0, sizeof d);
+    d.in_type = cls == mxINT16_CLASS ? QDAS_DEMOD_I16 : cls == mxSINGLE_CLASS ? (cplx ? QDAS_DEMOD_C64 : QDAS_DEMOD_F32) : (cplx ? QDAS_DEMOD_C128 : QDAS_DEMOD_F64);
+    d.device = -1;
+    const size_t np = mxGetNumberOfElements(prhs[2]);
+    const double Tn = num_at(prhs[2], 0, "prm"), fc = num_at(prhs[2], 1, "prm"), fs = num_at(prhs[2], 2, "prm"), ratio = num_at(prhs[2], 3, "prm");
+    const double gdiv = np > 4 ? num_at(prhs[2], 4, "prm") : 1.0;
+    if (!(Tn >= 0.0) || Tn != floor(Tn) || !(ratio >= 1.0) || ratio != floor(ratio) || !(gdiv >= 1.0) || gdiv != floor(gdiv) || !(fs > 0.0))
+        CFAIL("demod: prm = [T fc fs ratio gdiv] with fs > 0, an integer T >= 0 and positive integers ratio, gdiv.");
+    const uint64_t nx = (uint64_t)mxGetNumberOfElements(xa);
+    d.T = (uint64_t)Tn; d.C = d.T ? nx / d.T : 0;
+    if (d.T ? nx % d.T != 0 : nx != 0) CFAIL("demod: x holds %llu samples, not traces of T = %llu.", (unsigned long long)nx, (unsigned long long)d.T);
+    d.K = (uint64_t)mxGetNumberOfElements(prhs[1]); d.R = (uint64_t)ratio;
+    d.G = (uint64_t)mxGetNumberOfElements(prhs[3]); d.gdiv = (uint64_t)gdiv;
+    const uint64_t J = qdas_demod_len(d.T, d.R);
+    d.x_ld = d.T; d.out_ld = J;
+    d.fc_over_fs = fc / fs; d.step = fc * ratio / fs;
+    const int dbl = cls == mxDOUBLE_CLASS;
+    const mxClassID ocls = dbl ? mxDOUBLE_CLASS : mxSINGLE_CLASS;
+    const mwSize dims[2] = {(mwSize)J, (mwSize)d.C};
+    if (d.K == 0 || d.G == 0) CFAIL("demod: b and t0 must not be empty.");
+    if (J * d.C == 0) {
+        const int rc = qdas_demod(&d, NULL, NULL, NULL);                                             /* (an empty call is still validated) */
+        if (rc) CFAIL("%s", qdas_last_error());
+        release_devargs();
+        return mxCreateNumericArray(2, dims, ocls, mxCOMPLEX);
+    }
+    /* the taps in the data's precision and the start phases frac(fc t0), staged on the device */
+    const size_t rs = dbl ? 8 : 4;
+    (void)num_at(prhs[1], 0, "b"); (void)num_at(prhs[3], 0, "t0");      /* whatever raises (the class of b / t0, the device blocks) does so before the host blocks exist: */
+    void *db = dev_extra((size_t)d.K * rs), *dc = dev_extra((size_t)d.G * sizeof(double));      /* num_at's refusals do not depend on the index below numel */
+    void *hb = malloc((size_t)d.K * rs);
+    double *hc = (double *)malloc((size_t)d.G * sizeof(double));
+    if (!hb || !hc) { free(hb); free(hc); CFAIL("demod: out of memory."); }
+    for (uint64_t k = 0; k < d.K; ++k) { const double v = num_at(prhs[1], (mwSize)k, "b"); if (dbl) ((double *)hb)[k] = v; else ((float *)hb)[k] = (float)v; }
+    for (uint64_t k = 0; k < d.G; ++k) { const double c = fc * num_at(prhs[3], (mwSize)k, "t0"); hc[k] = c - floor(c); }
+    int rc = qdas_device_copy(db, hb, (size_t)d.K * rs, 0, -1);
+    if (!rc) rc = qdas_device_copy(dc, hc, (size_t)d.G * sizeof(double), 0, -1);
+    free(hb); free(hc);
+    if (rc) CFAIL("%s", qdas_last_error());
+    d.cyc0 = (const double *)dc;
+    int dev = 0;
+    const size_t es = cls == mxINT16_CLASS ? 2 : (dbl ? 8 : 4) * (cplx ? 2 : 1), bytes = (size_t)(J * d.C) * rs * 2;
+    const void *x = dev_in(xa, (size_t)nx * es, "x", &dev);
+    mxArray *host;
+    void *out = dev_out(2, dims, ocls, 1, dev, bytes, &host);
+    return finish(qdas_demod(&d, x, db, out), host, bytes);
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
 #ifdef QDAS_MEX_GPU
     mxInitGPU();
@@ -1163,6 +1228,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "rayintegrals")) { cmd_rayintegrals(nlhs, plhs, nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "raybackproject")) { cmd_raybackproject(nlhs, plhs, nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "scanconvert")) { plhs[0] = cmd_scanconvert(nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "demod")) { plhs[0] = cmd_demod(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();
         } else mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unknown command '%s'.", cmd);

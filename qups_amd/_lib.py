@@ -41,7 +41,7 @@ SYMBOLS = (
     "qdas_pwznxcorr", "qdas_pwznxcorr_time_tile", "qdas_pwznxcorr_lds_bytes", "qdas_refocus", "qdas_refocus_work_bytes",
     "qdas_raypaths_slots", "qdas_raypaths_weights", "qdas_raypaths_integrate", "qdas_raypaths_backproject",
     "qdas_eikonal3", "qdas_eikonal3_tables", "qdas_eikonal3_work_bytes", "qdas_eikonal3_pass_cap",
-    "qdas_scanconvert",
+    "qdas_scanconvert", "qdas_demod", "qdas_demod_len",
 )
 
 
@@ -173,6 +173,17 @@ class ScanconvertDesc(C.Structure):
                 ("queue", C.c_void_p)]
 
 
+DEMOD_I16, DEMOD_F32, DEMOD_C64, DEMOD_F64, DEMOD_C128 = 0, 1, 2, 3, 4
+DEMOD_MAX_K, DEMOD_MAX_R, DEMOD_TILE = 1024, 4096, 256
+
+
+class DemodDesc(C.Structure):
+    _fields_ = [("T", C.c_uint64), ("C", C.c_uint64), ("K", C.c_uint64), ("R", C.c_uint64), ("x_ld", C.c_uint64), ("out_ld", C.c_uint64),
+                ("in_type", C.c_int32), ("out_half", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32),
+                ("fc_over_fs", C.c_double), ("step", C.c_double), ("cyc0", C.c_void_p), ("gdiv", C.c_uint64), ("G", C.c_uint64),
+                ("queue", C.c_void_p)]
+
+
 class QdasError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libqdas error {code}: {msg}")
@@ -255,6 +266,9 @@ def lib():
     L.qdas_raypaths_integrate.argtypes = [C.POINTER(RaypathsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_raypaths_backproject.argtypes = [C.POINTER(RaypathsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_scanconvert.argtypes = [C.POINTER(ScanconvertDesc), C.c_void_p, C.c_void_p]
+    L.qdas_demod.argtypes = [C.POINTER(DemodDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qdas_demod_len.argtypes = [C.c_uint64, C.c_uint64]
+    L.qdas_demod_len.restype = C.c_uint64
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64
     L.qdas_shift_sum.argtypes = [C.POINTER(ShiftDesc), C.c_void_p, C.c_void_p, C.c_void_p]

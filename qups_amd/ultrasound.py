@@ -286,6 +286,47 @@ class ChannelData:
         idx[ax] = slice(0, None, ratio)
         return ChannelData(d[tuple(idx)].contiguous(), self.t0, self.fs / ratio, self.order)
 
+    def demod(self, fc: float, ratio: int, b, out_half=False):
+        """``downmix(fc)`` -> ``filter(b)`` -> ``downsample(ratio)`` in ONE pass over the record (``qdas_demod``, ``qups_amd/csrc/demod.hip``): the
+        reference's recipe for baseband imaging (the example in the help text of ``downmix``, ``src/ChannelData.m:757-807``), to be followed by
+        ``DAS(us, chd, fmod=fc)``.  ``b``: real FIR taps (:meth:`getLowpassFilter`).  The result has ``t0 - (K - 1) / 2 / fs`` (a per-transmit ``t0``
+        keeps its shape) and ``fs / ratio``; any ``order`` is accepted and kept.  For real data the result carries half the analytic amplitude, exactly as
+        the composition does (``2 * b`` restores it).  ``out_half``: complex32 data, what ``DAS(..., prec='halfT')`` takes."""
+        import torch
+        from .demod import demod
+        d = self._torch_data()
+        ax = self.order.index("T")
+        if not d.is_cuda:
+            if not torch.cuda.is_available():
+                raise RuntimeError("qups_amd: no HIP device visible -- demod has no CPU fallback")
+            d = d.cuda()
+        t0 = np.asarray(self.t0, float)
+        t0m = t0
+        if t0.size > 1:
+            if t0.ndim > d.ndim or any(a not in (1, b_) for a, b_ in zip(t0.shape, d.shape)) or (t0.ndim > ax and t0.shape[ax] != 1):
+                raise DasError("demod: t0 must be a scalar or broadcast against the data (and not vary along time)")
+            t0m = np.moveaxis(t0.reshape(t0.shape + (1,) * (d.ndim - t0.ndim)), ax, 0)
+        K = int(b.numel()) if hasattr(b, "numel") else int(np.size(b))
+        y = demod(d.movedim(ax, 0), fc, self.fs, t0m, b, ratio, out_half=out_half)
+        L = (K - 1) / 2.0
+        return ChannelData(y.movedim(0, ax), t0 - L / self.fs if np.ndim(self.t0) else float(self.t0) - L / self.fs, self.fs / int(ratio), self.order)
+
+    def getLowpassFilter(self, cutoff: float, N: int = 25):
+        """``N + 1`` real taps of a low-pass FIR filter with cutoff ``cutoff`` [Hz] at this data's ``fs`` (reference ``src/ChannelData.m:833-856``:
+        ``designfilt('lowpassfir', 'FilterOrder', N, 'CutoffFrequency', cutoff, 'DesignMethod', 'window')``) from ``scipy.signal.firwin`` with its
+        Hamming window -- the window design ``designfilt`` documents.  There is no MATLAB to pin the taps against: the tests hold them to the closed
+        form (Hamming-windowed sinc, unit gain at DC, symmetric taps)."""
+        from .demod import lowpass_taps
+        return lowpass_taps(cutoff, self.fs, N)
+
+    def getPassbandFilter(self, bw, N: int = 25):
+        """``N + 1`` real taps of a band-pass FIR filter between ``bw[0]`` and ``bw[-1]`` [Hz] (reference ``src/ChannelData.m:808-832``:
+        ``designfilt('bandpassfir', ..., 'DesignMethod', 'window')``) from ``scipy.signal.firwin`` (Hamming window).  As for :meth:`getLowpassFilter` the
+        tests hold the taps to the closed form: the difference of two windowed sincs, unit gain at the band centre, symmetric taps."""
+        from .demod import passband_taps
+        bw = np.asarray(bw, float).reshape(-1)
+        return passband_taps((bw[0], bw[-1]), self.fs, N)
+
     def sample(self, tau, interp="linear", w=1, sdim=None, fmod=0.0, **kw):
         """``y = sample(chd, tau, interp, w, sdim, fmod)`` (reference ``src/ChannelData.m:1230-1336``): ``tau`` holds TIMES and
         broadcasts against ``T x N x M x F...`` in every dimension but the first; sample indices ``(tau - t0) * fs`` (``:1317``),
