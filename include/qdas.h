@@ -794,6 +794,49 @@ typedef struct qdas_demod_desc {
 uint64_t qdas_demod_len(uint64_t T, uint64_t R);   /* J = ceil(T / R); 0 for R = 0 */
 int qdas_demod(const qdas_demod_desc *d, const void *x, const void *b, void *out);
 
+/* ---- Rational-rate polyphase FIR (resample.hip): the reference's resample, filtfilt and the FIR part of its time-axis DSP (src/ChannelData.m:1059-1094,
+ * :890-909) as ONE formula.  For x of T samples x C traces (time contiguous, trace c at x + c x_ld), real taps h[0 .. K-1], integers p, q >= 1 (they need not
+ * be coprime), an offset off >= 0 and an output count J:
+ *   out[j + c out_ld] = sum_i h[off + j q - i p] X_c[i],   j = 0 .. J-1,   over every integer i with 0 <= off + j q - i p < K.
+ * X[i] = x[i] for 0 <= i < T.  Outside the record edge = QDAS_RESAMPLE_ZERO gives X[i] = 0; edge = QDAS_RESAMPLE_ODD gives the odd reflection
+ * X[-i] = 2 x[0] - x[i], X[T-1+i] = 2 x[T-1] - x[T-1-i], and the call is refused (QDAS_EINVAL) unless every index an output reads lies in [-(T-1), 2(T-1)].
+ *   upfirdn(h, x, p, q):  off = 0, J = qdas_upfirdn_len(T, K, p, q) = ceil(((T-1) p + K) / q)            (scipy.signal.upfirdn)
+ *   resample(x, p, q):    K odd, off = (K-1)/2, J = qdas_resample_len(T, p, q) = ceil(T p / q), ZERO      (MATLAB's uniform syntax, scipy's resample_poly)
+ *   filtfilt(b, x):       p = q = 1, h = b * flip(b) (2 K_b - 1 taps), off = K_b - 1, J = T, ODD           (MATLAB's and scipy's filtfilt for an FIR b)
+ *   a plain FIR at any integer offset: p = q = 1.
+ * TYPES.  in_type QDAS_RESAMPLE_I16 | _F32 | _C64: fp32 products and sums, h is float32, out is float32 (I16, F32: int16 is widened while staging) or complex64.
+ * QDAS_RESAMPLE_F64 | _C128: fp64, h is float64, out is float64 or complex128.  h: DEVICE vector of K real taps.  One accumulator per output, taps of a phase
+ * in ascending order, no rounding but the FMAs' (and the one of a reflected sample).
+ * A sample no output reads is never multiplied, and no sample meets a zero coefficient: a NaN at x[i] reaches exactly the outputs with
+ * 0 <= off + j q - i p < K.  Every output element is written exactly once, out_ld padding is not touched, no atomics, no work space: bit-reproducible.
+ * `queue` is a hipStream_t; the call is asynchronous on it and synchronises nothing.
+ * All validation happens on the host before any HIP call: a null descriptor, an unknown in_type or edge, p = 0, q = 0, K = 0, x_ld < T, out_ld < J, and -- for
+ * a call that has work -- T = 0, a null x, h or out, and the ODD reach rule: QDAS_EINVAL.  J C = 0: QDAS_OK, nothing is launched, the pointers may be NULL.
+ * LIMITS: K <= QDAS_RESAMPLE_MAX_K = 8192, p, q <= QDAS_RESAMPLE_MAX_PQ = 4096; the K taps and the span of one output ((K-1)/p + 1 samples) within 64 KiB of
+ * LDS -- every K <= 2730 fits in every type at every p, more with p >= 2 or narrower data (int16 and float32: K = 8192 at every p); a workgroup
+ * takes the largest power of two of outputs, 1024 at most, whose span ceil((TJ-1) q / p) + (K-1)/p + 1 fits beside the taps (40 KiB down to 64 outputs, 64 KiB
+ * below); C ceil(J / TJ) < 2^31; T, C, J, off, x_ld, out_ld < 2^40: QDAS_EUNSUPPORTED beyond. */
+#define QDAS_RESAMPLE_I16  0
+#define QDAS_RESAMPLE_F32  1
+#define QDAS_RESAMPLE_C64  2
+#define QDAS_RESAMPLE_F64  3
+#define QDAS_RESAMPLE_C128 4
+#define QDAS_RESAMPLE_ZERO 0
+#define QDAS_RESAMPLE_ODD  1
+#define QDAS_RESAMPLE_MAX_K  8192
+#define QDAS_RESAMPLE_MAX_PQ 4096
+typedef struct qdas_resample_desc {
+    uint64_t T, C, K, J;         /* samples per trace, traces, taps, outputs per trace          */
+    uint64_t p, q, off;          /* up, down, tap offset of output 0                            */
+    uint64_t x_ld, out_ld;       /* trace strides in elements (x_ld >= T, out_ld >= J)          */
+    int32_t  in_type, edge;      /* QDAS_RESAMPLE_I16 .. _C128; QDAS_RESAMPLE_ZERO | _ODD       */
+    int32_t  device, reserved;   /* HIP ordinal, -1 = current                                   */
+    void    *queue;              /* a hipStream_t                                               */
+} qdas_resample_desc;
+uint64_t qdas_resample_len(uint64_t T, uint64_t p, uint64_t q);              /* ceil(T p / q); 0 for q = 0            */
+uint64_t qdas_upfirdn_len(uint64_t T, uint64_t K, uint64_t p, uint64_t q);   /* ceil(((T-1) p + K) / q); 0 for q T = 0 */
+int qdas_resample(const qdas_resample_desc *d, const void *x, const void *h, void *out);
+
 /* ---- Pair-wise windowed zero-normalized cross-correlation (pwznxcorr.hip): the base-MATLAB branch of the reference's kern/pwznxcorr.m (iflt = false:
  * convn(., w, 'same'), a zero pad at the end of the record, circshift) for every lag in ONE launch.  With h = floor(W / 2), P = max|lags| when `pad` (else 0),
  * Tp = T + P, both records extended by P zeros, K(a)[s] = sum_k w[k] a[s + h - k] for s in [0, Tp) and a = 0 outside [0, Tp) (MATLAB's 'same'):

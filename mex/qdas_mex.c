@@ -77,6 +77,8 @@
  *         opts = [] | [pre db_floor fill] | a struct with those fields; described at cmd_scanconvert below.
  *   y       = qdas_mex('demod', x, b, [T fc fs ratio gdiv], t0)
  *         downmix -> filter -> downsample in one pass; described at cmd_demod below.
+ *   y       = qdas_mex('resample', x, h, [T p q off J edge])
+ *         rational-rate polyphase FIR: resample, upfirdn, FIR filtfilt; described at cmd_resample below.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
  * pass as device pointers and the result is a gpuArray.
  *
@@ -1175,6 +1177,63 @@ static mxArray *cmd_demod(int nrhs, const mxArray *prhs[]) {
     return finish(qdas_demod(&d, x, db, out), host, bytes);
 }
 
+/* y = qdas_mex('resample', x, h, prm) -- the rational-rate polyphase FIR (qdas_resample): y(j) = sum_i h(off + j q - i p) X(i) (0-based) over the taps that
+ * exist, J outputs per trace.  x: int16 | single | double (single, double: real or complex), T x C (any trailing dimensions count as traces) as MATLAB holds it:
+ * time fastest (a host array or, in a GPU build, a gpuArray).  h: the real taps, a host vector of any numeric class (converted to the data's precision).
+ * prm = [T p q off J edge], edge 0: zeros outside the record, 1: odd reflection (optional, default 0).  With h = resample's design (p h / sum(h), odd length K),
+ * off = (K - 1) / 2 and J = ceil(T p / q) this is MATLAB's uniform resample(x, p, q); with p = q = 1, h = conv(b, flip(b)), off = numel(b) - 1, J = T and
+ * edge = 1 it is filtfilt(b, 1, x); with off = 0 and J = ceil(((T - 1) p + K) / q), upfirdn(x, h, p, q).  y: J x C, single for int16 and single data, double
+ * for double, complex for complex x. */
+static mxArray *cmd_resample(int nrhs, const mxArray *prhs[]) {
+    if (nrhs != 3) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('resample', x, h, prm)");
+    const mxArray *xa = prhs[0];
+    const mxClassID cls = mxGetClassID(xa);
+    const int cplx = mxIsComplex(xa) ? 1 : 0;
+    if ((cls != mxDOUBLE_CLASS && cls != mxSINGLE_CLASS && cls != mxINT16_CLASS) || (cls == mxINT16_CLASS && cplx))
+        mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "resample: x must be int16 (real), single or double.");
+    qdas_resample_desc d;
+    memset(&d, 0, sizeof d);
+    d.in_type = cls == mxINT16_CLASS ? QDAS_RESAMPLE_I16 : cls == mxSINGLE_CLASS ? (cplx ? QDAS_RESAMPLE_C64 : QDAS_RESAMPLE_F32) : (cplx ? QDAS_RESAMPLE_C128 : QDAS_RESAMPLE_F64);
+    d.device = -1;
+    const size_t np = mxGetNumberOfElements(prhs[2]);
+    const double Tn = num_at(prhs[2], 0, "prm"), pn = num_at(prhs[2], 1, "prm"), qn = num_at(prhs[2], 2, "prm"), on = num_at(prhs[2], 3, "prm"), Jn = num_at(prhs[2], 4, "prm");
+    const double en = np > 5 ? num_at(prhs[2], 5, "prm") : 0.0;
+    if (!(Tn >= 0.0) || Tn != floor(Tn) || !(pn >= 1.0) || pn != floor(pn) || !(qn >= 1.0) || qn != floor(qn) || !(on >= 0.0) || on != floor(on) ||
+        !(Jn >= 0.0) || Jn != floor(Jn) || (en != 0.0 && en != 1.0) || Tn >= 1e15 || pn >= 1e15 || qn >= 1e15 || on >= 1e15 || Jn >= 1e15)
+        CFAIL("resample: prm = [T p q off J edge] with integers T, off, J >= 0, p, q >= 1 and edge 0 | 1.");
+    const uint64_t nx = (uint64_t)mxGetNumberOfElements(xa);
+    d.T = (uint64_t)Tn; d.C = d.T ? nx / d.T : 0;
+    if (d.T ? nx % d.T != 0 : nx != 0) CFAIL("resample: x holds %llu samples, not traces of T = %llu.", (unsigned long long)nx, (unsigned long long)d.T);
+    d.K = (uint64_t)mxGetNumberOfElements(prhs[1]);
+    d.p = (uint64_t)pn; d.q = (uint64_t)qn; d.off = (uint64_t)on; d.J = (uint64_t)Jn; d.edge = (int32_t)en;
+    d.x_ld = d.T; d.out_ld = d.J;
+    const int dbl = cls == mxDOUBLE_CLASS;
+    const mxClassID ocls = dbl ? mxDOUBLE_CLASS : mxSINGLE_CLASS;
+    const mwSize dims[2] = {(mwSize)d.J, (mwSize)d.C};
+    if (d.K == 0) CFAIL("resample: h must not be empty.");
+    if (d.J * d.C == 0) {
+        const int rc = qdas_resample(&d, NULL, NULL, NULL);                                          /* (an empty call is still validated) */
+        if (rc) CFAIL("%s", qdas_last_error());
+        release_devargs();
+        return mxCreateNumericArray(2, dims, ocls, cplx ? mxCOMPLEX : mxREAL);
+    }
+    const size_t rs = dbl ? 8 : 4;
+    (void)num_at(prhs[1], 0, "h");                                      /* whatever raises (the class of h, the device block) does so before the host block exists */
+    void *dh = dev_extra((size_t)d.K * rs);
+    void *hh = malloc((size_t)d.K * rs);
+    if (!hh) CFAIL("resample: out of memory.");
+    for (uint64_t k = 0; k < d.K; ++k) { const double v = num_at(prhs[1], (mwSize)k, "h"); if (dbl) ((double *)hh)[k] = v; else ((float *)hh)[k] = (float)v; }
+    const int rc = qdas_device_copy(dh, hh, (size_t)d.K * rs, 0, -1);
+    free(hh);
+    if (rc) CFAIL("%s", qdas_last_error());
+    int dev = 0;
+    const size_t es = cls == mxINT16_CLASS ? 2 : rs * (cplx ? 2 : 1), bytes = (size_t)(d.J * d.C) * rs * (cplx ? 2 : 1);
+    const void *x = dev_in(xa, (size_t)nx * es, "x", &dev);
+    mxArray *host;
+    void *out = dev_out(2, dims, ocls, cplx, dev, bytes, &host);
+    return finish(qdas_resample(&d, x, dh, out), host, bytes);
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
 #ifdef QDAS_MEX_GPU
     mxInitGPU();
@@ -1229,6 +1288,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "raybackproject")) { cmd_raybackproject(nlhs, plhs, nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "scanconvert")) { plhs[0] = cmd_scanconvert(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "demod")) { plhs[0] = cmd_demod(nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "resample")) { plhs[0] = cmd_resample(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();
         } else mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unknown command '%s'.", cmd);

@@ -41,7 +41,7 @@ SYMBOLS = (
     "qdas_pwznxcorr", "qdas_pwznxcorr_time_tile", "qdas_pwznxcorr_lds_bytes", "qdas_refocus", "qdas_refocus_work_bytes",
     "qdas_raypaths_slots", "qdas_raypaths_weights", "qdas_raypaths_integrate", "qdas_raypaths_backproject",
     "qdas_eikonal3", "qdas_eikonal3_tables", "qdas_eikonal3_work_bytes", "qdas_eikonal3_pass_cap",
-    "qdas_scanconvert", "qdas_demod", "qdas_demod_len",
+    "qdas_scanconvert", "qdas_demod", "qdas_demod_len", "qdas_resample", "qdas_resample_len", "qdas_upfirdn_len",
 )
 
 
@@ -184,6 +184,17 @@ class DemodDesc(C.Structure):
                 ("queue", C.c_void_p)]
 
 
+RESAMPLE_I16, RESAMPLE_F32, RESAMPLE_C64, RESAMPLE_F64, RESAMPLE_C128 = 0, 1, 2, 3, 4
+RESAMPLE_ZERO, RESAMPLE_ODD = 0, 1
+RESAMPLE_MAX_K, RESAMPLE_MAX_PQ = 8192, 4096
+
+
+class ResampleDesc(C.Structure):
+    _fields_ = [("T", C.c_uint64), ("C", C.c_uint64), ("K", C.c_uint64), ("J", C.c_uint64), ("p", C.c_uint64), ("q", C.c_uint64), ("off", C.c_uint64),
+                ("x_ld", C.c_uint64), ("out_ld", C.c_uint64), ("in_type", C.c_int32), ("edge", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32),
+                ("queue", C.c_void_p)]
+
+
 class QdasError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libqdas error {code}: {msg}")
@@ -269,6 +280,11 @@ def lib():
     L.qdas_demod.argtypes = [C.POINTER(DemodDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_demod_len.argtypes = [C.c_uint64, C.c_uint64]
     L.qdas_demod_len.restype = C.c_uint64
+    L.qdas_resample.argtypes = [C.POINTER(ResampleDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qdas_resample_len.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
+    L.qdas_resample_len.restype = C.c_uint64
+    L.qdas_upfirdn_len.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.qdas_upfirdn_len.restype = C.c_uint64
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64
     L.qdas_shift_sum.argtypes = [C.POINTER(ShiftDesc), C.c_void_p, C.c_void_p, C.c_void_p]

@@ -311,6 +311,57 @@ class ChannelData:
         L = (K - 1) / 2.0
         return ChannelData(y.movedim(0, ax), t0 - L / self.fs if np.ndim(self.t0) else float(self.t0) - L / self.fs, self.fs / int(ratio), self.order)
 
+    def _device_data(self, what):
+        import torch
+        d = self._torch_data()
+        if not d.is_cuda:
+            if not torch.cuda.is_available():
+                raise RuntimeError(f"qups_amd: no HIP device visible -- {what} has no CPU fallback")
+            d = d.cuda()
+        return d
+
+    def resample(self, fs: float, n: int = 10, beta: float = 5.0, p=None, q=None):
+        """The data at the sampling frequency ``fs`` (reference ``src/ChannelData.m:1059-1094``) by a rational-rate polyphase FIR on the device
+        (``qdas_resample``, ``qups_amd/csrc/resample.hip``): MATLAB's uniform ``resample(x, p, q, n, beta)`` with its default Kaiser-windowed design.
+        ``p / q = Fraction(fs / self.fs).limit_denominator(4096)``; when that does not reproduce ``fs`` to 1e-9 relative the call raises and asks for explicit
+        ``p, q``.  ``t0`` is unchanged and the new ``fs`` is ``self.fs p / q``; any ``order`` is accepted and kept.
+        TWO DEVIATIONS from the reference: it computes in double and casts back, this computes in the data's precision; and it calls MATLAB's non-uniform
+        syntax ``resample(x, t, fs)``, whose linear pre-interpolation and 1 % rate tolerance are not reproduced."""
+        from fractions import Fraction
+        from .resample import resample
+        if (p is None) != (q is None):
+            raise DasError("resample: give both p and q, or neither")
+        if p is None:
+            if not (fs > 0 and np.isfinite(fs)):
+                raise DasError("resample: fs must be positive")
+            fr = Fraction(float(fs) / float(self.fs)).limit_denominator(4096)
+            p, q = fr.numerator, fr.denominator
+            if p < 1 or abs(self.fs * p / q - fs) > 1e-9 * abs(fs):
+                raise DasError(f"resample: fs / self.fs = {float(fs) / float(self.fs)!r} is no ratio p / q with q <= 4096 (the nearest, {p} / {q}, misses fs by more "
+                               "than 1e-9): pass p and q explicitly")
+        fr = Fraction(int(p), int(q))
+        d = self._device_data("resample")
+        ax = self.order.index("T")
+        y = resample(d.movedim(ax, 0), fr.numerator, fr.denominator, n, beta)
+        return ChannelData(y.movedim(0, ax), self.t0, self.fs * fr.numerator / fr.denominator, self.order)
+
+    def filtfilt(self, b, dim=None, a=None, sos=None):
+        """Zero-phase filtering along time with the real FIR taps ``b`` (reference ``src/ChannelData.m:890-909``: ``filtfilt(D, x)``; ``t0`` is unchanged) in
+        ONE pass on the device (``qups_amd.resample.filtfilt``).  An IIR filter (``a`` or ``sos``) is not built and raises.  Any ``order`` is accepted and
+        kept.  DEVIATION: the reference computes in double and casts back; this computes in the data's precision."""
+        from .resample import filtfilt
+        if a is not None or sos is not None:
+            raise DasError("filtfilt: an IIR filter (a, sos) is not built -- only FIR taps b")
+        ax = self.order.index("T") if dim is None else int(dim) - 1
+        d = self._device_data("filtfilt")
+        y = filtfilt(b, d.movedim(ax, 0))
+        return ChannelData(y.movedim(0, ax), self.t0, self.fs, self.order)
+
+    def fftfilt(self, b, dim=None):
+        """``fftfilt(D, x)`` along time for the FIR taps ``b`` (reference ``src/ChannelData.m:910-934``), ``t0 -= (K - 1) / 2 / fs`` (``:931-933``).  For an FIR
+        filter the result equals :meth:`filter`'s, so this routes there: ``qdas_convd`` already picks its FFT path for long filters."""
+        return self.filter(b, dim)
+
     def getLowpassFilter(self, cutoff: float, N: int = 25):
         """``N + 1`` real taps of a low-pass FIR filter with cutoff ``cutoff`` [Hz] at this data's ``fs`` (reference ``src/ChannelData.m:833-856``:
         ``designfilt('lowpassfir', 'FilterOrder', N, 'CutoffFrequency', cutoff, 'DesignMethod', 'window')``) from ``scipy.signal.firwin`` with its

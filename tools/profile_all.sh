@@ -93,6 +93,7 @@ bash tools/dma_ab.sh 2 > $OUT/dma_ab_c3_raw.txt 2>&1
 python tools/migration_time.py > profiles/migration_time.txt 2>/dev/null
 python tools/raybackproject_time.py > profiles/raybackproject_time.txt 2>/dev/null
 python tools/demod_time.py > profiles/demod_time.txt 2>/dev/null
+python tools/resample_time.py > profiles/resample_time.txt 2>/dev/null
 # ---- PCIe-inclusive: host-resident frames through the C ABI, and the int16 RF -> hilbert -> band-pass -> DAS chain for a stream
 python tools/host_frames.py > $OUT/host_frames.txt 2>/dev/null
 python tools/pipeline_bench.py c3 12 64 > $OUT/pipeline_bench.txt 2>/dev/null; python tools/pipeline_bench.py c2 12 64 >> $OUT/pipeline_bench.txt 2>/dev/null
