@@ -837,6 +837,58 @@ uint64_t qdas_resample_len(uint64_t T, uint64_t p, uint64_t q);              /* 
 uint64_t qdas_upfirdn_len(uint64_t T, uint64_t K, uint64_t p, uint64_t q);   /* ceil(((T-1) p + K) / q); 0 for q T = 0 */
 int qdas_resample(const qdas_resample_desc *d, const void *x, const void *h, void *out);
 
+/* ---- 2-D acoustic FDTD (fdtd.hip): a linear, lossless, first-order solver on a staggered grid, the part the reference delegates to external solvers
+ * (src/UltrasoundSystem.m:2458-3170 kspaceFirstOrder, :1042-1460 fullwaveSim).  FDTD of order 2R in space, NOT k-space pseudospectral.  Nz x Nx nodes (the
+ * PML included), z fastest, spacing h in both directions, V pulses stepped together.  p, rz, rx at (i, j); uz at (i + 1/2, j), ux at (i, j + 1/2).
+ *   D+f[i] = (1/h) sum_{k=1..R} a_k (f[i+k] - f[i-k+1])  (at i + 1/2),   D-g[i] = (1/h) sum_{k=1..R} a_k (g[i+k-1] - g[i-k])  (at i),
+ * anything outside the array reads as 0; a = (1), (9/8, -1/24), (1225/1024, -245/3072, 49/5120, -5/7168) for R = 1, 2, 4.  One step n = 0 .. Nt-1:
+ *   1. uz <- azs (azs uz - (dtrz / h) h D+z p),   ux <- axs (axs ux - (dtrx / h) h D+x p)         dtrz = dt / rho_sgz, dtrx = dt / rho_sgx
+ *   2. uz[src m] += src_wz[m] s[n, m, v],  ux[src m] += src_wx[m] s[n, m, v]   for n < Ts           src_wz = nz 2 c[src] dt / h (additive velocity source)
+ *   3. rz <- az (az rz - (dt / h) rho h D-z uz),  rx <- ax (ax rx - (dt / h) rho h D-x ux)
+ *   4. p = c2 (rz + rx)
+ *   5. rec[n rec_st + j rec_sn + v rec_sv] = p[sensor j]
+ * az, azs (Nz) and ax, axs (Nx) are the PML factors exp(-alpha dt / 2) at the nodes and at the staggered points, 1 inside.
+ * MEMORY.  The caller owns every byte; every pointer of qdas_fdtd_args is a DEVICE pointer.  States: element (i, j) of pulse v at v vstride + j ld + i
+ * (ld >= Nz, vstride >= Nx ld); the padding is not touched.  The medium maps are Nx x Nz dense.  s is Ts x M x V (pulse fastest).  src_node / sen_node hold
+ * j Nz + i; src_start / src_list and sen_start / sen_list are the per-tile lists qdas_fdtd_tile_lists makes on the host (a workgroup owns a tile of
+ * QDAS_FDTD_TZ x QDAS_FDTD_TX nodes and injects and records the points inside it behind its own update: two launches per step, no atomics, no flags;
+ * points must sit on distinct nodes).  The entry allocates nothing, synchronises nothing, captures no graph: it enqueues 2 Nt launches on `queue`
+ * (a hipStream_t).  Two runs give the same bits; pulses never mix (a NaN in pulse v stays there).
+ * dtype QDAS_F32 | QDAS_F64 (every array of that type); order = 2R in {2, 4, 8}.
+ * All validation happens on the host before any HIP call: a null descriptor or argument block, a dtype other than QDAS_F32 / QDAS_F64, Nz = 0 or Nx = 0,
+ * ld < Nz, vstride < Nx ld, dt_h or inv_h not finite and positive, and -- for a call that has work -- a null state, medium or PML pointer, M > 0 and Ts > 0
+ * with a null source pointer, N > 0 with a null sensor pointer, unknown flags: QDAS_EINVAL.  An order other than 2, 4, 8, Nz or Nx >= 2^31, ld >= 2^40,
+ * Nz Nx >= 2^31, V > 65535, M or N >= 2^31, Nt, Ts or a stride >= 2^40: QDAS_EUNSUPPORTED.  Nt = 0 or V = 0: QDAS_OK, nothing is launched, the pointers may
+ * be NULL.
+ * flags: QDAS_FDTD_ZERO -- the entry clears the Nz x Nx x V elements of each state array (not the padding) on `queue` before the first step: a start from
+ * rest for a caller without a device fill of its own (the MEX gateway). */
+#define QDAS_FDTD_TZ 64
+#define QDAS_FDTD_TX 16
+#define QDAS_FDTD_ZERO 1
+typedef struct qdas_fdtd_desc {
+    uint64_t Nz, Nx, V, Nt;            /* nodes with the PML, pulses, steps                          */
+    uint64_t ld, vstride;              /* state strides in elements: row (>= Nz), pulse (>= Nx ld)   */
+    uint64_t M, Ts, N;                 /* sources, rows of the source table, sensors                 */
+    uint64_t rec_st, rec_sn, rec_sv;   /* record strides in elements: step, sensor, pulse            */
+    double   dt_h, inv_h;              /* dt / h and 1 / h                                           */
+    int32_t  dtype, order;             /* QDAS_F32 | QDAS_F64; 2R: 2, 4 or 8                         */
+    int32_t  device, flags;            /* HIP ordinal, -1 = current; 0 | QDAS_FDTD_ZERO              */
+    void    *queue;                    /* a hipStream_t                                              */
+} qdas_fdtd_desc;
+typedef struct qdas_fdtd_args {
+    void *p, *uz, *ux, *rz, *rx;                       /* states, V x Nx x Nz (strided), updated in place */
+    const void *c2, *rho, *dtrz, *dtrx;                /* c^2, rho, dt / rho_sgz, dt / rho_sgx            */
+    const void *az, *azs, *ax, *axs;                   /* PML factors                                     */
+    const void *s, *src_wz, *src_wx;                   /* source table and per-source weights             */
+    const int32_t *src_node, *src_start, *src_list;
+    const int32_t *sen_node, *sen_start, *sen_list;
+    void *rec;
+} qdas_fdtd_args;
+uint64_t qdas_fdtd_tiles(uint64_t Nz, uint64_t Nx);      /* ceil(Nz / TZ) ceil(Nx / TX)                                                      */
+/* HOST helper: start[0 .. tiles] and list[0 .. n) from n HOST node indices; QDAS_EINVAL for a node outside the grid. Tile (tz, tx) is tx ceil(Nz / TZ) + tz. */
+int qdas_fdtd_tile_lists(uint64_t Nz, uint64_t Nx, uint64_t n, const int32_t *node, int32_t *start, int32_t *list);
+int qdas_fdtd(const qdas_fdtd_desc *d, const qdas_fdtd_args *a);
+
 /* ---- Pair-wise windowed zero-normalized cross-correlation (pwznxcorr.hip): the base-MATLAB branch of the reference's kern/pwznxcorr.m (iflt = false:
  * convn(., w, 'same'), a zero pad at the end of the record, circshift) for every lag in ONE launch.  With h = floor(W / 2), P = max|lags| when `pad` (else 0),
  * Tp = T + P, both records extended by P zeros, K(a)[s] = sum_k w[k] a[s + h - k] for s in [0, Tp) and a = 0 outside [0, Tp) (MATLAB's 'same'):

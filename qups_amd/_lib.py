@@ -42,6 +42,7 @@ SYMBOLS = (
     "qdas_raypaths_slots", "qdas_raypaths_weights", "qdas_raypaths_integrate", "qdas_raypaths_backproject",
     "qdas_eikonal3", "qdas_eikonal3_tables", "qdas_eikonal3_work_bytes", "qdas_eikonal3_pass_cap",
     "qdas_scanconvert", "qdas_demod", "qdas_demod_len", "qdas_resample", "qdas_resample_len", "qdas_upfirdn_len",
+    "qdas_fdtd", "qdas_fdtd_tiles", "qdas_fdtd_tile_lists",
 )
 
 
@@ -195,6 +196,24 @@ class ResampleDesc(C.Structure):
                 ("queue", C.c_void_p)]
 
 
+FDTD_TZ, FDTD_TX, FDTD_ZERO = 64, 16, 1
+
+
+class FdtdDesc(C.Structure):
+    _fields_ = [("Nz", C.c_uint64), ("Nx", C.c_uint64), ("V", C.c_uint64), ("Nt", C.c_uint64), ("ld", C.c_uint64), ("vstride", C.c_uint64),
+                ("M", C.c_uint64), ("Ts", C.c_uint64), ("N", C.c_uint64), ("rec_st", C.c_uint64), ("rec_sn", C.c_uint64), ("rec_sv", C.c_uint64),
+                ("dt_h", C.c_double), ("inv_h", C.c_double), ("dtype", C.c_int32), ("order", C.c_int32), ("device", C.c_int32), ("flags", C.c_int32),
+                ("queue", C.c_void_p)]
+
+
+FDTD_ARGS = ("p", "uz", "ux", "rz", "rx", "c2", "rho", "dtrz", "dtrx", "az", "azs", "ax", "axs", "s", "src_wz", "src_wx",
+             "src_node", "src_start", "src_list", "sen_node", "sen_start", "sen_list", "rec")
+
+
+class FdtdArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in FDTD_ARGS]
+
+
 class QdasError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libqdas error {code}: {msg}")
@@ -285,6 +304,10 @@ def lib():
     L.qdas_resample_len.restype = C.c_uint64
     L.qdas_upfirdn_len.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
     L.qdas_upfirdn_len.restype = C.c_uint64
+    L.qdas_fdtd.argtypes = [C.POINTER(FdtdDesc), C.POINTER(FdtdArgs)]
+    L.qdas_fdtd_tiles.argtypes = [C.c_uint64, C.c_uint64]
+    L.qdas_fdtd_tiles.restype = C.c_uint64
+    L.qdas_fdtd_tile_lists.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64
     L.qdas_shift_sum.argtypes = [C.POINTER(ShiftDesc), C.c_void_p, C.c_void_p, C.c_void_p]

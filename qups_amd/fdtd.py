@@ -1,0 +1,305 @@
+"""A 2-D acoustic FDTD channel-data simulator on the device: ``csrc/fdtd.hip`` behind :func:`fdtd` (arrays) and ``UltrasoundSystem.fdtdSim`` (objects).
+
+The scheme is linear, lossless and first order on a staggered grid, of order ``2R`` in space (``include/qdas.h`` states it in full; ``tests/fdtd_ref.py`` is
+its numpy restatement).  It follows the wrapper contract of the reference's ``kspaceFirstOrder`` (``src/UltrasoundSystem.m:2458-3170``) where that contract
+is about our objects -- grid, time step, sources, sensors, ``t0``, ``isosub``, ``field`` -- but the numerical method is FDTD, NOT k-space pseudospectral:
+absolute amplitude and dispersion are this discretisation's and are not matched to k-Wave.
+
+Everything the kernel reads is prepared here on the host in float64 (the extended medium, staggered densities, PML factors, the sampled source table, the
+per-tile point lists) and uploaded once; the states, the record and every table are torch tensors, so the C entry allocates nothing.  There is no CPU
+fallback: without the library or a device the call raises."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib
+from .das_spec import DasError
+
+__all__ = ["fdtd", "launch", "prepare", "time_step", "stability_limit", "tx_table", "pml_size", "pml_factors", "nearest_nodes", "iso_density", "grid_spacing",
+           "tile_lists", "COEFS", "TILE", "STATES"]
+
+COEFS = {1: (1.0,), 2: (9.0 / 8.0, -1.0 / 24.0), 4: (1225.0 / 1024.0, -245.0 / 3072.0, 49.0 / 5120.0, -5.0 / 7168.0)}
+TILE = (_lib.FDTD_TZ, _lib.FDTD_TX)
+
+
+def stability_limit(R: int) -> float:
+    """``c_max dt / h <= 1 / (sqrt(2) sum|a_k|)``: 0.707, 0.606 and 0.5497 for R = 1, 2, 4"""
+    return 1.0 / (math.sqrt(2.0) * sum(abs(a) for a in COEFS[int(R)]))
+
+
+def _order(order):
+    if order not in (2, 4, 8):
+        raise DasError(f"fdtd: order is 2, 4 or 8 (R = 1, 2, 4), got {order!r}")
+    return int(order) // 2
+
+
+def grid_spacing(z, x, y=None):
+    """``h`` of a uniform square grid; unequal or non-uniform spacing (beyond 1e-6 relative) and a non-singleton y are refused"""
+    z, x = np.asarray(z, np.float64).reshape(-1), np.asarray(x, np.float64).reshape(-1)
+    if y is not None and np.size(y) > 1:
+        raise DasError("fdtd: the grid has a non-singleton y; 3-D is not built")
+    if z.size < 2 or x.size < 2:
+        raise DasError("fdtd: the grid needs at least two nodes in z and in x")
+    dz, dx = np.diff(z), np.diff(x)
+    h = float(dz.mean())
+    if not h > 0 or np.abs(dz - h).max() > 1e-6 * h or np.abs(dx - h).max() > 1e-6 * h:
+        raise DasError(f"fdtd: the grid spacing must be uniform and equal in z and x (dz = {h:g}, dx = {float(dx.mean()):g})")
+    return h
+
+
+def time_step(fs, c_max, h, CFL_max=0.25, order=8):
+    """``(ratio, fs_, dt)`` (reference ``:2714-2729``): the largest step allowed is ``dt_cfl = CFL_max h / c_max``; ``ratio = max(1, ceil((1 / fs) / dt_cfl))
+    = max(1, ceil(c_max / (fs CFL_max h)))``, ``fs_ = ratio fs``, ``dt = 1 / fs_``; a ``dt`` above the scheme's stability limit is refused"""
+    R = _order(order)
+    if not (fs > 0 and c_max > 0 and h > 0 and CFL_max > 0):
+        raise DasError("fdtd: fs, c_max, h and CFL_max must be positive")
+    ratio = max(1, int(math.ceil(float(c_max) / (float(fs) * float(CFL_max) * float(h)) - 1e-12)))
+    fs_ = ratio * float(fs)
+    dt = 1.0 / fs_
+    if c_max * dt / h > stability_limit(R):
+        raise DasError(f"fdtd: c_max dt / h = {c_max * dt / h:.4f} is above the stability limit {stability_limit(R):.4f} of order {2 * R}")
+    return ratio, fs_, dt
+
+
+def _sample_cubic(w, idx):
+    """``w`` at the fractional 0-based indices ``idx`` with the Catmull-Rom cubic ``greens`` uses for its waveform; taps outside the record are 0 (float64)"""
+    w = np.asarray(w, np.float64).reshape(-1)
+    idx = np.asarray(idx, np.float64)
+    ti = np.floor(idx)
+    u = idx - ti
+    wt = 0.5 * np.stack([u * (-1.0 + u * (2.0 - u)), 2.0 + u * u * (3.0 * u - 5.0), u * (1.0 + u * (4.0 - 3.0 * u)), u * u * (u - 1.0)])
+    out = np.zeros(idx.shape)
+    for k in range(4):
+        t = ti.astype(np.int64) - 1 + k
+        ok = (t >= 0) & (t < w.size)
+        out += np.where(ok, wt[k] * w[np.clip(t, 0, w.size - 1)], 0.0)
+    return out
+
+
+def tx_table(waveform, wv_t0, wv_fs, delays, apod, fs_):
+    """``(s, txn0, txne)``: the source table ``T' x M x V`` in float64 (reference ``:2735-2741``).  ``del = -delays``;
+    ``txn0 = floor((wv_t0 + min del) fs_)``, ``txne = ceil((wv_tend + max del) fs_)``; ``s[n, m, v] = apod[m, v] w((txn0 + n) / fs_ - del[m, v])``"""
+    w = np.asarray(waveform, np.float64).reshape(-1)
+    dl = -np.asarray(delays, np.float64)
+    ap = np.asarray(apod, np.float64)
+    tend = wv_t0 + (w.size - 1) / wv_fs
+    txn0 = int(math.floor((wv_t0 + dl.min()) * fs_ + 1e-9))
+    txne = int(math.ceil((tend + dl.max()) * fs_ - 1e-9))
+    t = np.arange(txn0, txne + 1, dtype=np.float64)[:, None, None] / fs_
+    s = ap[None] * _sample_cubic(w, (t - dl[None] - wv_t0) * wv_fs)
+    return s, txn0, txne
+
+
+def _largest_prime_factor(n):
+    n, f, best = int(n), 2, 1
+    while f * f <= n:
+        while n % f == 0:
+            best, n = f, n // f
+        f += 1
+    return max(best, n) if n > 1 else best
+
+
+def pml_size(PML, Z, X):
+    """a scalar is taken as is; a pair ``[lo, hi]`` picks the size in that range whose ``Z + 2P`` and ``X + 2P`` have the smallest largest prime factor
+    (the first such size), as the reference does for its FFTs -- harmless here, kept for parity"""
+    if np.ndim(PML) == 0:
+        P = int(PML)
+        if P < 0 or P != PML:
+            raise DasError(f"fdtd: PML must be a non-negative integer, got {PML!r}")
+        return P
+    if np.size(PML) != 2:
+        raise DasError(f"fdtd: PML is a size or a range [lo, hi], got {PML!r}")
+    lo, hi = (int(v) for v in np.asarray(PML).reshape(-1))
+    if lo < 0 or hi < lo:
+        raise DasError(f"fdtd: PML is a size or a range [lo, hi], got {PML!r}")
+    return min(range(lo, hi + 1), key=lambda P: (max(_largest_prime_factor(Z + 2 * P), _largest_prime_factor(X + 2 * P)), P))
+
+
+def pml_factors(N, P, c_max, h, dt):
+    """``(A, A_staggered)`` of ``N`` nodes (the layer included): ``exp(-alpha dt / 2)``, ``alpha = 2 (c_max / h) (xi / P)^4``, ``xi`` the depth into the layer in
+    cells, evaluated at ``i`` and at ``i + 1/2``; 1 inside and for ``P = 0`` (float64)"""
+    i = np.arange(N, dtype=np.float64)
+    if P == 0:
+        return np.ones(N), np.ones(N)
+
+    def A(pos):
+        xi = np.maximum(np.maximum(P - pos, pos - (N - 1 - P)), 0.0)
+        return np.exp(-(2.0 * (c_max / h) * (xi / P) ** 4) * dt / 2.0)
+
+    return A(i), A(i + 0.5)
+
+
+def nearest_nodes(z, x, pos):
+    """``(iz, ix)`` of the nearest node per position; ``pos`` is ``3 x M`` with rows ``(x, y, z)``, as ``Transducer.positions()`` gives them, or ``2 x M``
+    with rows ``(z, x)``.  The reference's assertion applies when two positions share a node (``:2753-2768``)."""
+    z, x = np.asarray(z, np.float64).reshape(-1), np.asarray(x, np.float64).reshape(-1)
+    pos = np.asarray(pos, np.float64)
+    pz, px = (pos[2], pos[0]) if pos.shape[0] == 3 else (pos[0], pos[1])
+    iz = np.abs(pz[:, None] - z[None]).argmin(1)
+    ix = np.abs(px[:, None] - x[None]).argmin(1)
+    if len({(a, b) for a, b in zip(iz.tolist(), ix.tolist())}) != iz.size:
+        raise DasError("Elements are not unique; the Scan spacing or sizing may be too small.")
+    return iz.astype(np.int64), ix.astype(np.int64)
+
+
+def iso_density(c, c0, rho0):
+    """the iso-impedance medium of ``isosub``: ``rho_iso = c0 rho0 / c`` (reference ``:2706-2712``)"""
+    return float(c0) * float(rho0) / np.asarray(c, np.float64)
+
+
+def tile_lists(Nz, Nx, nodes):
+    """``(start, list)`` int32: the per-tile lists of the points at ``nodes`` (``j Nz + i``), from the library's host helper"""
+    L = _lib.lib()
+    nodes = np.ascontiguousarray(nodes, np.int32)
+    nt = int(L.qdas_fdtd_tiles(Nz, Nx))
+    start, lst = np.zeros(nt + 1, np.int32), np.zeros(max(nodes.size, 1), np.int32)
+    _lib.check(L.qdas_fdtd_tile_lists(Nz, Nx, nodes.size, nodes.ctypes.data if nodes.size else None, start.ctypes.data, lst.ctypes.data))
+    return start, lst[:nodes.size]
+
+
+def prepare(c, rho, h, dt, P):
+    """the kernel's host tables in float64 from the interior medium ``c``, ``rho`` (``Z x X``): a dict with ``Nz, Nx, c2, rho, dtrz, dtrx`` (``Nx x Nz``, z
+    fastest: extended by edge replication, the staggered density the mean of the two neighbours with the last row kept) and ``az, azs, ax, axs``"""
+    c, rho = np.asarray(c, np.float64), np.asarray(rho, np.float64)
+    if c.ndim != 2 or rho.shape != c.shape:
+        raise DasError(f"fdtd: c and rho are Z x X maps of one shape, got {c.shape} and {rho.shape}")
+    if not (np.isfinite(c).all() and np.isfinite(rho).all() and (c > 0).all() and (rho > 0).all()):
+        raise DasError("fdtd: c and rho must be finite and positive")
+    ce, re = np.pad(c, P, mode="edge"), np.pad(rho, P, mode="edge")
+    sgz, sgx = re.copy(), re.copy()
+    sgz[:-1] = 0.5 * (re[:-1] + re[1:])
+    sgx[:, :-1] = 0.5 * (re[:, :-1] + re[:, 1:])
+    Nz, Nx = ce.shape
+    c_max = float(c.max())
+    az, azs = pml_factors(Nz, P, c_max, h, dt)
+    ax, axs = pml_factors(Nx, P, c_max, h, dt)
+    T = lambda a: np.ascontiguousarray(a.T)
+    return dict(Nz=Nz, Nx=Nx, c=T(ce), c2=T(ce * ce), rho=T(re), dtrz=T(dt / sgz), dtrx=T(dt / sgx), az=az, azs=azs, ax=ax, axs=axs)
+
+
+def fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt, PML=20, order=8, prec="single", bsize=None, device=None, return_state=False, ld=None, prepare_only=False,
+         sen_nodes=None):
+    """``rec = fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt)``: ``Nt`` steps of the scheme on the grid ``z`` x ``x`` (``c``, ``rho``: ``Z x X``)
+    with ``PML`` cells added on every side.  ``src_pos`` / ``sen_pos``: positions (``3 x M`` rows x, y, z, or ``2 x M`` rows z, x) mapped to their nearest
+    nodes; ``src_normal``: ``2 x M`` rows ``(nz, nx)``; ``s``: the source table ``T' x M x V`` (host array or tensor).  Returns the record ``Nt x N x V`` (a
+    device tensor of ``prec``), and with ``return_state`` also a dict of the five state arrays ``V x Nx x Nz`` after the last step.  ``sen_nodes``: the
+    sensors' interior nodes ``(iz, ix)`` given directly, in place of ``sen_pos`` (``field``: every node).  ``bsize``: pulses per call, to bound the memory of
+    the states: without ``return_state`` ONE set of ``bsize x Nx x ld`` state arrays serves every block.  ``ld``: the row stride of the state arrays (default ``Nz``).  ``prepare_only``: ``(meta, tables, s)`` on the device for :func:`launch`, nothing run.
+    Queued on torch's current stream."""
+    import torch
+    if prec not in ("single", "double"):
+        raise DasError("fdtd: prec must be 'single' or 'double'")
+    R = _order(order)
+    h = grid_spacing(z, x)
+    zc, xc = np.asarray(z, np.float64).reshape(-1), np.asarray(x, np.float64).reshape(-1)
+    c = np.asarray(c.detach().cpu().numpy() if hasattr(c, "detach") else c, np.float64)
+    rho = np.asarray(rho.detach().cpu().numpy() if hasattr(rho, "detach") else rho, np.float64)
+    if c.shape != (zc.size, xc.size):
+        raise DasError(f"fdtd: c is Z x X = {zc.size} x {xc.size}, got {c.shape}")
+    P = pml_size(PML, zc.size, xc.size)
+    dt = float(dt)
+    if not (dt > 0 and math.isfinite(dt)):
+        raise DasError("fdtd: dt must be positive")
+    if c.max() * dt / h > stability_limit(R):
+        raise DasError(f"fdtd: c_max dt / h = {c.max() * dt / h:.4f} is above the stability limit {stability_limit(R):.4f} of order {2 * R}")
+    tab = prepare(c, rho, h, dt, P)
+    Nz, Nx = tab["Nz"], tab["Nx"]
+    s_host = None if isinstance(s, torch.Tensor) else np.asarray(s, np.float64)
+    if (s.ndim if s_host is None else s_host.ndim) != 3:
+        raise DasError("fdtd: the source table is T' x M x V")
+    Ts, M, V = (int(v) for v in (s.shape if s_host is None else s_host.shape))
+    siz, six = nearest_nodes(zc, xc, src_pos) if M else (np.zeros(0, np.int64),) * 2
+    if sen_nodes is not None:
+        niz, nix = (np.asarray(a, np.int64).reshape(-1) for a in sen_nodes)
+        if niz.size != nix.size or (niz.size and (niz.min() < 0 or niz.max() >= zc.size or nix.min() < 0 or nix.max() >= xc.size)):
+            raise DasError("fdtd: sen_nodes are (iz, ix) inside the grid")
+    else:
+        niz, nix = nearest_nodes(zc, xc, sen_pos) if np.size(sen_pos) else (np.zeros(0, np.int64),) * 2
+    nrm = np.asarray(src_normal, np.float64).reshape(2, -1)
+    if siz.size != M or nrm.shape[1] != M:
+        raise DasError(f"fdtd: {siz.size} source positions and {nrm.shape[1]} normals for a table of M = {M} sources")
+    N, Nt = int(niz.size), int(Nt)
+    if Nt < 0:
+        raise DasError("fdtd: Nt must not be negative")
+    src_node = ((six + P) * Nz + (siz + P)).astype(np.int32)
+    sen_node = ((nix + P) * Nz + (niz + P)).astype(np.int32)
+    csrc = tab["c"].reshape(-1)[src_node] if M else np.zeros(0)
+    wz, wx = nrm[0] * 2.0 * csrc * dt / h, nrm[1] * 2.0 * csrc * dt / h
+
+    if device is None:
+        device = s.device if s_host is None and s.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise DasError("fdtd: needs a device (there is no CPU fallback in this package)")
+    rdt = torch.float32 if prec == "single" else torch.float64
+    up = lambda a, dt_=None: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt_ or rdt)
+    src_start, src_list = tile_lists(Nz, Nx, src_node)
+    sen_start, sen_list = tile_lists(Nz, Nx, sen_node)
+    tb = {k: up(tab[k]) for k in ("c2", "rho", "dtrz", "dtrx", "az", "azs", "ax", "axs")}
+    tb.update(src_wz=up(wz), src_wx=up(wx))
+    tb.update({k: up(v, torch.int32) for k, v in (("src_node", src_node), ("src_start", src_start), ("src_list", src_list), ("sen_node", sen_node),
+                                                  ("sen_start", sen_start), ("sen_list", sen_list))})
+    s_dev = (s if s_host is None else up(s_host)).to(device=dev, dtype=rdt)
+    ld = Nz if ld is None else int(ld)
+    if ld < Nz:
+        raise DasError(f"fdtd: ld = {ld} is less than Nz = {Nz}")
+    meta = dict(Nz=Nz, Nx=Nx, Nt=Nt, ld=ld, M=M, Ts=Ts, N=N, dt_h=dt / h, inv_h=1.0 / h, double=prec == "double", order=2 * R)
+    if prepare_only:
+        return meta, tb, s_dev
+    rec = torch.empty((Nt, N, V), dtype=rdt, device=dev)
+    bs = V if not bsize else max(1, min(int(bsize), V))
+    states = {k: [] for k in STATES}
+    pool = None                                                  # the one set of state arrays every block works in, unless the states are wanted
+    with torch.cuda.device(dev):
+        for v0 in range(0, V, bs) if V else ():
+            Vb = min(bs, V - v0)
+            if return_state or pool is None:
+                pool = {k: torch.empty((Vb, Nx, ld), dtype=rdt, device=dev) for k in STATES}
+            st = {k: pool[k][:Vb] for k in STATES}
+            for k in STATES:
+                st[k].zero_()
+            launch(meta, tb, st, s_dev[:, :, v0:v0 + Vb].contiguous(), rec, v0)
+            if return_state:
+                for k in STATES:
+                    states[k].append(st[k][:, :, :Nz])
+    if not return_state:
+        return rec
+    cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+    empty = torch.zeros((0, Nx, Nz), dtype=rdt, device=dev)
+    return rec, {k: (cat(v) if v else empty) for k, v in states.items()}
+
+
+STATES = ("p", "uz", "ux", "rz", "rx")
+
+
+def launch(meta, tb, st, sb, rec, v0=0, stream=None):
+    """one call of ``qdas_fdtd``: ``meta`` the sizes and scalars, ``tb`` the device tables by the names of ``qdas_fdtd_args``, ``st`` the five state tensors
+    ``Vb x Nx x ld`` (zero for a start from rest), ``sb`` the source table ``T' x M x Vb`` (contiguous), ``rec`` the whole record ``Nt x N x V`` of which the
+    pulses ``v0 .. v0 + Vb - 1`` are written.  ``stream``: a ``torch.cuda.Stream`` (default: the current one).  Only enqueues."""
+    import torch
+    dev = st["p"].device
+    Vb = int(st["p"].shape[0])
+    d = _lib.FdtdDesc()
+    d.Nz, d.Nx, d.V, d.Nt, d.ld, d.vstride = meta["Nz"], meta["Nx"], Vb, meta["Nt"], meta["ld"], meta["Nx"] * meta["ld"]
+    d.M, d.Ts, d.N = meta["M"], meta["Ts"], meta["N"]
+    d.rec_st, d.rec_sn, d.rec_sv = (int(v) for v in rec.stride())
+    d.dt_h, d.inv_h = meta["dt_h"], meta["inv_h"]
+    d.dtype, d.order = (0 if meta["double"] else 1), meta["order"]                  # QDAS_F64 | QDAS_F32
+    d.device = dev.index if dev.index is not None else torch.cuda.current_device()
+    d.flags = int(meta.get("flags", 0))                                           # _lib.FDTD_ZERO: the entry clears the states itself
+    stream = stream or torch.cuda.current_stream(dev)
+    d.queue = C.c_void_p(stream.cuda_stream)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    a = _lib.FdtdArgs()
+    for k in STATES:
+        setattr(a, k, ptr(st[k]))
+    for k, t in tb.items():
+        setattr(a, k, ptr(t))
+    a.s = ptr(sb)
+    a.rec = C.c_void_p(rec.data_ptr() + v0 * rec.stride(2) * rec.element_size()) if rec.numel() else None
+    _lib.check(_lib.lib().qdas_fdtd(C.byref(d), C.byref(a)))
+    if sb.numel():
+        sb.record_stream(stream)

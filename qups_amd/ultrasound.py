@@ -8,6 +8,7 @@ and foci, the channel data with its time axis -- and the argument marshalling of
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -530,6 +531,82 @@ class UltrasoundSystem:
                         R0=R0, interp=interp)
         chd = ChannelData(y.contiguous(), t0, fs, "TNM")
         return self.focusTx(chd, self.seq, interp=interp) if focus else chd
+
+    def fdtdSim(self, c, rho=None, cgrd: Scan | None = None, *, waveform, wv_t0, wv_fs, rx_impulse=None, rx_t0=0.0, c0=None, rho0=None, T=None, PML=20,
+                CFL_max=0.25, order=8, isosub=False, field=False, bsize=None, prec="single", ElemMapMethod="nearest", plan_only=False):
+        """``chd = fdtdSim(us, c, rho, cgrd)``: channel data that travelled through the medium ``c``, ``rho`` (``Z x X`` on the Cartesian scan ``cgrd``, by
+        default this system's scan), from a 2-D acoustic FDTD solver on the device (``qups_amd/fdtd.py`` -> ``qdas_fdtd``).  It follows the wrapper contract of
+        the reference's ``kspaceFirstOrder`` (``src/UltrasoundSystem.m:2458-3170``) -- the time step from ``CFL_max`` as an integer fraction of ``1 / us.fs``
+        (``:2714-2729``), the transmit table from the sequence's delays and apodization (``:2735-2741``), elements on their nearest nodes (``:2753-2768``),
+        additive velocity sources along the element normals (``:2874-2878``), ``T`` defaulting to one round trip across the grid (``:2890``), ``t0``
+        (``:2904``), ``isosub`` (``:2706-2712``), ``field`` (``:2471-2482``) -- but the method is FDTD of order ``order`` in space, NOT k-space pseudospectral:
+        absolute amplitude and dispersion are this discretisation's and are not matched to k-Wave.
+
+        The transmit waveform is an input (samples, start time, sampling frequency), as in :meth:`greens`; ``rx_impulse`` (samples at ``wv_fs`` starting at
+        ``rx_t0``) is applied afterwards with ``convd`` in ``'full'`` shape (``:3069-3070``).  ``rho = None``: ``rho0`` everywhere, ``rho0 = c0 / 1.5`` (the
+        reference's default medium, ``:2638``).  ``PML``: a size, or a range ``[lo, hi]``.  ``bsize``: pulses per solver call.  The record is ``T x N x V`` at
+        ``fs_ = ratio us.fs``, as the reference returns it: the caller downsamples.  ``field=True``: the pressure of the whole interior grid per step,
+        ``T x (Z X) x V`` (sensors = all nodes, ``Z`` slowest, no receive impulse), refused above 2 GiB.  ``plan_only``: the wrapper arithmetic alone, a dict
+        (no device needed).  Not built: 3-D, absorption, nonlinearity, ``'linear'`` and ``karray-*`` element mapping, sensor directivity."""
+        from . import fdtd as F
+        if ElemMapMethod != "nearest":
+            if ElemMapMethod in ("linear", "karray-direct", "karray-depend"):
+                raise NotImplementedError(f"fdtdSim: ElemMapMethod '{ElemMapMethod}' is not built; only 'nearest' is")
+            raise DasError(f"fdtdSim: unknown ElemMapMethod {ElemMapMethod!r}")
+        if prec not in ("single", "double"):
+            raise DasError("fdtdSim: prec must be 'single' or 'double'")
+        cgrd = cgrd or self.scan
+        if cgrd.axes is None or cgrd.axes.get("kind") != "cartesian":
+            raise DasError("fdtdSim: cgrd must be a Cartesian scan made by Scan.cartesian (order 'ZXY').")
+        z, x = cgrd.axes["z"], cgrd.axes["x"]
+        h = F.grid_spacing(z, x, cgrd.axes["y"])
+        Z, X = z.size, x.size
+        c0 = float(self.seq.c0 if c0 is None else c0)
+        rho0 = float(c0 / 1.5 if rho0 is None else rho0)
+        c = np.asarray(c.detach().cpu().numpy() if hasattr(c, "detach") else c, np.float64).reshape(Z, X) if np.size(c) == Z * X else None
+        if c is None:
+            raise DasError(f"fdtdSim: c must have the grid's size Z x X = {Z} x {X}")
+        if rho is None:
+            rho = np.full((Z, X), rho0)
+        rho = np.asarray(rho.detach().cpu().numpy() if hasattr(rho, "detach") else rho, np.float64)
+        if rho.size != Z * X:
+            raise DasError(f"fdtdSim: rho must have the grid's size Z x X = {Z} x {X}")
+        rho = rho.reshape(Z, X)
+        if self.fs is None:
+            raise DasError("fdtdSim: the system needs a sampling frequency fs")
+        ratio, fs_, dt = F.time_step(self.fs, c.max(), h, CFL_max, order)
+        s, txn0, txne = F.tx_table(waveform, wv_t0, wv_fs, self.seq.delays(self.tx), self.seq.apodization(self.tx), fs_)
+        if T is None:
+            T = 2.0 * math.hypot(z[-1] - z[0], x[-1] - x[0]) / c0
+        Nt = 1 + int(math.floor((float(T) + (txne - txn0) / fs_) * fs_ + 1e-9))
+        P = F.pml_size(PML, Z, X)
+        rx_t0 = float(rx_t0) if (rx_impulse is not None and not field) else 0.0
+        plan = dict(h=h, ratio=ratio, fs_=fs_, dt=dt, txn0=txn0, txne=txne, Nt=Nt, t0=txn0 / fs_ + rx_t0, P=P, Nz=Z + 2 * P, Nx=X + 2 * P, T=float(T),
+                    rho=rho, rho_iso=F.iso_density(c, c0, rho0) if isosub else None)
+        nrm = np.stack([self.tx.normals[2], self.tx.normals[0]])
+        V = s.shape[2]
+        if field:
+            sen, sen_nodes = np.zeros((2, 0)), tuple(np.indices((Z, X)).reshape(2, -1))      # every node, Z slowest: no search
+            if Nt * Z * X * V * (4 if prec == "single" else 8) > 2 ** 31:
+                raise DasError(f"fdtdSim: field=True would return {Nt} x {Z * X} x {V} values, above 2 GiB; shorten T or coarsen the grid")
+        else:
+            sen, sen_nodes = self.rx.positions(), None
+        siz, six = F.nearest_nodes(z, x, self.tx.positions())           # (raises the reference's assertion before any device work)
+        plan.update(src_nodes=(siz, six), sen_nodes=F.nearest_nodes(z, x, sen) if not field else None)
+        if plan_only:
+            return plan
+        run = lambda r: F.fdtd(c, r, z, x, self.tx.positions(), nrm, s, sen, Nt, dt, PML=P, order=order, prec=prec, bsize=bsize, sen_nodes=sen_nodes)
+        y = run(rho)
+        if isosub:
+            y = y - run(plan["rho_iso"])
+        if rx_impulse is not None and not field:
+            import torch
+            from .convd import convd
+            w = np.asarray(rx_impulse, np.float64).reshape(-1)
+            nr = int(math.floor((w.size - 1) / wv_fs * fs_ + 1e-9)) + 1
+            taps = F._sample_cubic(w, np.arange(nr) / fs_ * wv_fs)
+            y = convd(y, torch.from_numpy(taps).to(device=y.device, dtype=y.dtype).reshape(-1, 1, 1), 1, "full")
+        return ChannelData(y, plan["t0"], fs_, "TNM")
 
     def _num_tx(self, chd):
         return int(chd.data.shape[chd.order.index("M")])
