@@ -889,6 +889,66 @@ uint64_t qdas_fdtd_tiles(uint64_t Nz, uint64_t Nx);      /* ceil(Nz / TZ) ceil(N
 int qdas_fdtd_tile_lists(uint64_t Nz, uint64_t Nx, uint64_t n, const int32_t *node, int32_t *start, int32_t *list);
 int qdas_fdtd(const qdas_fdtd_desc *d, const qdas_fdtd_args *a);
 
+/* ---- 3-D acoustic FDTD (fdtd3.hip): the scheme of qdas_fdtd with a third axis -- linear, lossless, first order in time, of order 2R in space (R = 1, 2, 4)
+ * on a staggered grid -- for channel data through volumes (the reference's kspaceFirstOrder picks kspaceFirstOrder3D for a grid of three dimensions,
+ * src/UltrasoundSystem.m:2929-2948).  FDTD, NOT k-space pseudospectral.
+ * GRID.  Nz x Nx x Ny nodes of spacing h in every direction, the P PML cells on all six faces included (the medium extended by edge replication); z is
+ * fastest, then x, then y: node (k Nx + j) Nz + i, the memory order of a Scan.cartesian(x, z, y) grid ('ZXY').  V pulses are stepped together.
+ * FIELDS.  p, rz, rx, ry at (i, j, k); uz at (i + 1/2, j, k), ux at (i, j + 1/2, k), uy at (i, j, k + 1/2).  The staggered density of an axis is the mean of
+ * the two neighbours along it, the last one kept.  Along an axis, with anything outside the array read as 0,
+ *   D+f[i] = (1/h) sum_{k=1..R} a_k (f[i+k] - f[i-k+1])  (at i + 1/2),   D-g[i] = (1/h) sum_{k=1..R} a_k (g[i+k-1] - g[i-k])  (at i),
+ * a = (1), (9/8, -1/24), (1225/1024, -245/3072, 49/5120, -5/7168) for R = 1, 2, 4 (the sums run k = 1 .. R in this order).  One step n = 0 .. Nt-1:
+ *   1. u_a <- A+_a (A+_a u_a - (dtr_a / h) h D+_a p)         for a in {z, x, y}; dtr_a = dt / rho_sg,a; A+_a = azs | axs | ays
+ *   2. u_a[src m] += src_w_a[m] s[n, m, v]   for n < Ts        src_w_a = n_a 2 c[src] dt / h (additive velocity source along the normal (nz, nx, ny))
+ *   3. r_a <- A_a (A_a r_a - (dt / h) rho h D-_a u_a)          A_a = az | ax | ay
+ *   4. p = c2 ((rz + rx) + ry), in this order of addition
+ *   5. rec[n rec_st + j rec_sn + v rec_sv] = p[sensor j]
+ * The PML factors are A = exp(-alpha dt / 2), alpha = 2 (c_max / h) (xi / P)^4, xi the depth into the layer in cells, at the nodes (A) and at the staggered
+ * points (A+), 1 inside.  Every table is made in float64 on the host and rounded once to `dtype`.
+ * STABILITY.  c_max dt / h <= 1 / (sqrt(3) sum|a_k|) = 0.5774, 0.4949, 0.4488 for R = 1, 2, 4 (the callers check; the entry does not know c_max).
+ * MEMORY.  The caller owns every byte; every pointer of qdas_fdtd3_args is a DEVICE pointer.  States: element (i, j, k) of pulse v at
+ * v vstride + k pstride + j ld + i (ld >= Nz, pstride >= Nx ld, vstride >= Ny pstride); the padding is not touched.  The medium maps are Ny x Nx x Nz dense.
+ * s is Ts x M x V (pulse fastest).  src_node / sen_node hold (k Nx + j) Nz + i; src_start / src_list and sen_start / sen_list are the per-brick lists
+ * qdas_fdtd3_brick_lists makes on the host.  A workgroup owns a brick of QDAS_FDTD3_TZ x QDAS_FDTD3_TX x QDAS_FDTD3_TY nodes of one pulse, marches through it
+ * along y, and injects and records the points inside it behind its own update: two launches per step, no atomics, no flags; points must sit on distinct
+ * nodes.  The entry allocates nothing, uses no work space, synchronises nothing, captures no graph: it enqueues 2 Nt launches on `queue` (a hipStream_t).
+ * Two runs give the same bits; pulses never mix (a NaN in pulse v stays there).
+ * dtype QDAS_F32 | QDAS_F64 (every array of that type); order = 2R in {2, 4, 8}.
+ * All validation happens on the host before any HIP call: a null descriptor or argument block, a dtype other than QDAS_F32 / QDAS_F64, an extent of 0,
+ * ld < Nz, pstride < Nx ld, vstride < Ny pstride, dt_h or inv_h not finite and positive, unknown flags, and -- for a call that has work -- a null state,
+ * medium or PML pointer, M > 0 and Ts > 0 with a null source pointer, N > 0 with a null sensor pointer: QDAS_EINVAL.  An order other than 2, 4, 8, an extent
+ * >= 2^31, Nz Nx Ny >= 2^31 (node indices are int32), ld >= 2^40, pstride >= 2^44, vstride >= 2^46, V > 65535, M or N >= 2^31, Nt, Ts or a record stride
+ * >= 2^40: QDAS_EUNSUPPORTED.  Nt = 0 or V = 0: QDAS_OK, nothing is launched, the pointers may be NULL.
+ * flags: QDAS_FDTD3_ZERO -- the entry clears the Nz x Nx x Ny x V elements of each state array (not the padding) on `queue` before the first step. */
+#define QDAS_FDTD3_TZ 64
+#define QDAS_FDTD3_TX 8
+#define QDAS_FDTD3_TY 8
+#define QDAS_FDTD3_ZERO 1
+typedef struct qdas_fdtd3_desc {
+    uint64_t Nz, Nx, Ny, V, Nt;        /* nodes with the PML, pulses, steps                                            */
+    uint64_t ld, pstride, vstride;     /* state strides in elements: row (>= Nz), plane (>= Nx ld), pulse (>= Ny pstride) */
+    uint64_t M, Ts, N;                 /* sources, rows of the source table, sensors                                   */
+    uint64_t rec_st, rec_sn, rec_sv;   /* record strides in elements: step, sensor, pulse                              */
+    double   dt_h, inv_h;              /* dt / h and 1 / h                                                             */
+    int32_t  dtype, order;             /* QDAS_F32 | QDAS_F64; 2R: 2, 4 or 8                                           */
+    int32_t  device, flags;            /* HIP ordinal, -1 = current; 0 | QDAS_FDTD3_ZERO                               */
+    void    *queue;                    /* a hipStream_t                                                                */
+} qdas_fdtd3_desc;
+typedef struct qdas_fdtd3_args {
+    void *p, *uz, *ux, *uy, *rz, *rx, *ry;             /* states, V x Ny x Nx x Nz (strided), updated in place */
+    const void *c2, *rho, *dtrz, *dtrx, *dtry;         /* c^2, rho, dt / rho_sg of the three axes              */
+    const void *az, *azs, *ax, *axs, *ay, *ays;        /* PML factors                                          */
+    const void *s, *src_wz, *src_wx, *src_wy;          /* source table and per-source weights                  */
+    const int32_t *src_node, *src_start, *src_list;
+    const int32_t *sen_node, *sen_start, *sen_list;
+    void *rec;
+} qdas_fdtd3_args;
+uint64_t qdas_fdtd3_bricks(uint64_t Nz, uint64_t Nx, uint64_t Ny);   /* ceil(Nz / TZ) ceil(Nx / TX) ceil(Ny / TY)                                       */
+/* HOST helper: start[0 .. bricks] and list[0 .. n) from n HOST node indices; QDAS_EINVAL for a node outside the grid.  Brick (bz, bx, by) is
+ * (by ceil(Nx / TX) + bx) ceil(Nz / TZ) + bz. */
+int qdas_fdtd3_brick_lists(uint64_t Nz, uint64_t Nx, uint64_t Ny, uint64_t n, const int32_t *node, int32_t *start, int32_t *list);
+int qdas_fdtd3(const qdas_fdtd3_desc *d, const qdas_fdtd3_args *a);
+
 /* ---- Pair-wise windowed zero-normalized cross-correlation (pwznxcorr.hip): the base-MATLAB branch of the reference's kern/pwznxcorr.m (iflt = false:
  * convn(., w, 'same'), a zero pad at the end of the record, circshift) for every lag in ONE launch.  With h = floor(W / 2), P = max|lags| when `pad` (else 0),
  * Tp = T + P, both records extended by P zeros, K(a)[s] = sum_k w[k] a[s + h - k] for s in [0, Tp) and a = 0 outside [0, Tp) (MATLAB's 'same'):

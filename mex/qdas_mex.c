@@ -81,6 +81,8 @@
  *         rational-rate polyphase FIR: resample, upfirdn, FIR filtfilt; described at cmd_resample below.
  *   rec     = qdas_mex('fdtd', med, pml, s, src, sen, [Nz Nx V Nt dt_h inv_h order])
  *         2-D acoustic FDTD from rest, the record of the sensors; described at cmd_fdtd below.
+ *   rec     = qdas_mex('fdtd3', med, pml, s, src, sen, [Nz Nx Ny V Nt dt_h inv_h order])
+ *         the same through a volume; described at cmd_fdtd3 below.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
  * pass as device pointers and the result is a gpuArray.
  *
@@ -1329,6 +1331,99 @@ static mxArray *cmd_fdtd(int nrhs, const mxArray *prhs[]) {
     return finish(qdas_fdtd(&d, &a), host, bytes);
 }
 
+/* rec = qdas_mex('fdtd3', med, pml, s, src, sen, prm) -- Nt steps of the 3-D acoustic FDTD scheme (qdas_fdtd3, include/qdas.h) from rest, on tables the caller
+ * prepared (qups_amd/fdtd3.py `prepare` is the recipe).  The 'fdtd' command with a third axis:
+ * med: Nz x Nx x Ny x 5, single or double (every real array follows its class): c^2, rho, dt / rho_sgz, dt / rho_sgx, dt / rho_sgy, z fastest, then x, then y
+ * (a host array or, in a GPU build, a gpuArray).  pml: [az; azs; ax; axs; ay; ays], 2 Nz + 2 Nx + 2 Ny values.  s: V x M x T' (pulse fastest), the source
+ * table.  src: 4 x M host array, per source [node; wz; wx; wy] with node = (k Nx + j) Nz + i (0-based) and wz = nz 2 c dt / h.  sen: N host values, the
+ * sensors' nodes (0-based).  prm = [Nz Nx Ny V Nt dt_h inv_h order], order 2, 4 or 8 (optional, default 8).  rec: Nt x N x V of the class of med.
+ * The states are the gateway's own scratch, cleared on the device (QDAS_FDTD3_ZERO: the gateway has no device fill); sources and sensors must sit on distinct
+ * nodes.  M = 0 (src empty) is allowed: the record is then all zeros. */
+static mxArray *cmd_fdtd3(int nrhs, const mxArray *prhs[]) {
+    if (nrhs != 6) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('fdtd3', med, pml, s, src, sen, prm)");
+    const mxClassID cls = mxGetClassID(prhs[0]);
+    if ((cls != mxDOUBLE_CLASS && cls != mxSINGLE_CLASS) || mxIsComplex(prhs[0])) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtd3: med must be real single or double.");
+    if (mxGetClassID(prhs[1]) != cls || mxGetClassID(prhs[2]) != cls || mxIsComplex(prhs[1]) || mxIsComplex(prhs[2]))
+        mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtd3: pml and s must be real and of the class of med.");
+    const size_t np = mxGetNumberOfElements(prhs[5]);
+    const double zn = num_at(prhs[5], 0, "prm"), xn = num_at(prhs[5], 1, "prm"), yn = num_at(prhs[5], 2, "prm"), vn = num_at(prhs[5], 3, "prm"), tn = num_at(prhs[5], 4, "prm");
+    const double on = np > 7 ? num_at(prhs[5], 7, "prm") : 8.0;
+    if (!(zn >= 1.0) || zn != floor(zn) || !(xn >= 1.0) || xn != floor(xn) || !(yn >= 1.0) || yn != floor(yn) || !(vn >= 0.0) || vn != floor(vn) || !(tn >= 0.0) ||
+        tn != floor(tn) || on != floor(on) || zn * xn * yn >= 2147483648.0 || vn > 65535.0 || tn >= 1e12 || !(fabs(on) < 1e6))
+        mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtd3: prm = [Nz Nx Ny V Nt dt_h inv_h order] with integers Nz, Nx, Ny >= 1, Nz Nx Ny < 2^31, 0 <= V <= 65535, Nt >= 0.");
+    qdas_fdtd3_desc d;
+    memset(&d, 0, sizeof d);
+    d.Nz = (uint64_t)zn; d.Nx = (uint64_t)xn; d.Ny = (uint64_t)yn; d.V = (uint64_t)vn; d.Nt = (uint64_t)tn;
+    d.dt_h = num_at(prhs[5], 5, "prm"); d.inv_h = num_at(prhs[5], 6, "prm");
+    d.dtype = cls == mxDOUBLE_CLASS ? QDAS_F64 : QDAS_F32; d.order = (int32_t)on; d.device = -1;
+    d.flags = QDAS_FDTD3_ZERO;                                                                      /* the states are scratch of this call: the entry clears them on the device */
+    d.ld = d.Nz; d.pstride = d.Nz * d.Nx; d.vstride = d.pstride * d.Ny;
+    const size_t cells = (size_t)d.vstride, npml = 2 * (size_t)(d.Nz + d.Nx + d.Ny), rs = cls == mxDOUBLE_CLASS ? 8 : 4;
+    d.M = (uint64_t)(mxGetNumberOfElements(prhs[3]) / 4); d.N = (uint64_t)mxGetNumberOfElements(prhs[4]);
+    if (mxGetNumberOfElements(prhs[3]) % 4) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtd3: src is 4 x M: [node; wz; wx; wy] per source.");
+    if (mxGetNumberOfElements(prhs[0]) != 5 * cells) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtd3: med holds %llu values, not Nz x Nx x Ny x 5.", (unsigned long long)mxGetNumberOfElements(prhs[0]));
+    if (mxGetNumberOfElements(prhs[1]) != npml) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtd3: pml holds %llu values, not 2 Nz + 2 Nx + 2 Ny.", (unsigned long long)mxGetNumberOfElements(prhs[1]));
+    const uint64_t ns = (uint64_t)mxGetNumberOfElements(prhs[2]), MV = d.M * d.V;
+    d.Ts = MV ? ns / MV : 0;
+    if (MV ? ns % MV != 0 : ns != 0) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtd3: s holds %llu values, not V x M x T' with V = %llu, M = %llu.", (unsigned long long)ns, (unsigned long long)d.V, (unsigned long long)d.M);
+    d.rec_st = 1; d.rec_sn = d.Nt; d.rec_sv = d.Nt * d.N;
+    const mwSize dims[3] = {(mwSize)d.Nt, (mwSize)d.N, (mwSize)d.V};
+    if (d.Nt * d.V == 0 || d.N == 0) {
+        const int rc = d.N == 0 ? QDAS_OK : qdas_fdtd3(&d, NULL);                                     /* (an empty call is still validated) */
+        if (rc) CFAIL("%s", qdas_last_error());
+        release_devargs();
+        return mxCreateNumericArray(3, dims, cls, mxREAL);
+    }
+    /* the host side: node lists, per-brick lists and the weights, in one integer and one real block */
+    const uint64_t nb = qdas_fdtd3_bricks(d.Nz, d.Nx, d.Ny);
+    const size_t ni = (size_t)(2 * d.M + 2 * d.N + 2 * (nb + 1)), nr = (size_t)(3 * d.M);
+    if (d.M) (void)num_at(prhs[3], 0, "src");
+    (void)num_at(prhs[4], 0, "sen");                   /* whatever raises does so before the host blocks exist */
+    int32_t *hi = (int32_t *)calloc(ni ? ni : 1, sizeof(int32_t));
+    void *hr = calloc(nr ? nr : 1, rs);
+    if (!hi || !hr) { free(hi); free(hr); CFAIL("fdtd3: out of memory."); }
+    int32_t *src_node = hi, *src_start = src_node + d.M, *src_list = src_start + nb + 1, *sen_node = src_list + d.M, *sen_start = sen_node + d.N, *sen_list = sen_start + nb + 1;
+    int bad = 0;
+    for (uint64_t m = 0; m < d.M; ++m) {
+        const double nd = num_at(prhs[3], (mwSize)(4 * m), "src");
+        if (!(nd >= 0.0) || nd != floor(nd) || nd >= (double)cells) bad = 1; else src_node[m] = (int32_t)nd;
+        for (int r = 0; r < 3; ++r) {
+            const double w = num_at(prhs[3], (mwSize)(4 * m + 1 + (uint64_t)r), "src");
+            if (rs == 8) ((double *)hr)[(size_t)r * d.M + m] = w; else ((float *)hr)[(size_t)r * d.M + m] = (float)w;
+        }
+    }
+    for (uint64_t j = 0; j < d.N; ++j) {
+        const double nd = num_at(prhs[4], (mwSize)j, "sen");
+        if (!(nd >= 0.0) || nd != floor(nd) || nd >= (double)cells) bad = 1; else sen_node[j] = (int32_t)nd;
+    }
+    if (bad || qdas_fdtd3_brick_lists(d.Nz, d.Nx, d.Ny, d.M, src_node, src_start, src_list) || qdas_fdtd3_brick_lists(d.Nz, d.Nx, d.Ny, d.N, sen_node, sen_start, sen_list)) {
+        free(hi); free(hr);
+        CFAIL("fdtd3: the nodes of src and sen are integers in [0, Nz Nx Ny).");
+    }
+    const size_t sb = cells * (size_t)d.V * rs;
+    char *di = (char *)dev_extra(ni * sizeof(int32_t)), *dr = (char *)dev_extra((nr ? nr : 1) * rs), *ds = (char *)dev_extra(7 * sb);
+    int rc = qdas_device_copy(di, hi, ni * sizeof(int32_t), 0, -1);
+    if (!rc && nr) rc = qdas_device_copy(dr, hr, nr * rs, 0, -1);
+    free(hi); free(hr);
+    if (rc) CFAIL("%s", qdas_last_error());
+    int dev = 0;
+    const char *med = (const char *)dev_in(prhs[0], 5 * cells * rs, "med", &dev), *pml = (const char *)dev_in(prhs[1], npml * rs, "pml", &dev);
+    const void *sp = dev_in(prhs[2], (size_t)ns * rs, "s", &dev);
+    qdas_fdtd3_args a;
+    memset(&a, 0, sizeof a);
+    a.p = ds; a.uz = ds + sb; a.ux = ds + 2 * sb; a.uy = ds + 3 * sb; a.rz = ds + 4 * sb; a.rx = ds + 5 * sb; a.ry = ds + 6 * sb;
+    a.c2 = med; a.rho = med + cells * rs; a.dtrz = med + 2 * cells * rs; a.dtrx = med + 3 * cells * rs; a.dtry = med + 4 * cells * rs;
+    a.az = pml; a.azs = pml + d.Nz * rs; a.ax = pml + 2 * d.Nz * rs; a.axs = pml + (2 * d.Nz + d.Nx) * rs;
+    a.ay = pml + 2 * (d.Nz + d.Nx) * rs; a.ays = pml + (2 * (d.Nz + d.Nx) + d.Ny) * rs;
+    a.s = sp; a.src_wz = dr; a.src_wx = dr + d.M * rs; a.src_wy = dr + 2 * d.M * rs;
+    const int32_t *dii = (const int32_t *)di;
+    a.src_node = dii; a.src_start = dii + d.M; a.src_list = a.src_start + nb + 1; a.sen_node = a.src_list + d.M; a.sen_start = a.sen_node + d.N; a.sen_list = a.sen_start + nb + 1;
+    const size_t bytes = (size_t)(d.Nt * d.N * d.V) * rs;
+    mxArray *host;
+    a.rec = dev_out(3, dims, cls, 0, dev, bytes, &host);
+    return finish(qdas_fdtd3(&d, &a), host, bytes);
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
 #ifdef QDAS_MEX_GPU
     mxInitGPU();
@@ -1385,6 +1480,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "demod")) { plhs[0] = cmd_demod(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "resample")) { plhs[0] = cmd_resample(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "fdtd")) { plhs[0] = cmd_fdtd(nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "fdtd3")) { plhs[0] = cmd_fdtd3(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();
         } else mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "unknown command '%s'.", cmd);

@@ -23,7 +23,8 @@ from .scanconvert import scan_convert, scan_convert3  # noqa: F401,E402
 from .demod import demod  # noqa: F401,E402  (the call, under the module's name: the module itself is importlib.import_module("qups_amd.demod"))
 from .resample import filtfilt, resample, resample_taps, upfirdn  # noqa: F401,E402  (resample is the call; the module is importlib.import_module("qups_amd.resample"))
 from . import fdtd  # noqa: F401,E402  (the module: fdtd.fdtd is the call, UltrasoundSystem.fdtdSim the wrapper)
+from . import fdtd3  # noqa: F401,E402  (fdtd3.fdtd3: the same through volumes)
 from .ultrasound import ChannelData, Scan, Sequence, Transducer, UltrasoundSystem  # noqa: F401,E402
 
 __all__ = ["das_spec", "DasPlan", "MultiDevicePlan", "DasProblem", "DasError", "build_problem", "parse_options", "das_lut", "sample2sep",
-           "wsinterpd2", "convd", "slsc", "dmas", "cohfac", "pcf", "pwznxcorr", "msfm", "msfm3d", "adjoint", "migration", "refocus", "wbilerpg", "ray_integrals", "ray_backproject", "ray_sart", "rayPaths", "globalAverageC", "scan_convert", "scan_convert3", "demod", "resample", "resample_taps", "upfirdn", "filtfilt", "fdtd", "UltrasoundSystem", "Transducer", "Sequence", "Scan", "ChannelData"]
+           "wsinterpd2", "convd", "slsc", "dmas", "cohfac", "pcf", "pwznxcorr", "msfm", "msfm3d", "adjoint", "migration", "refocus", "wbilerpg", "ray_integrals", "ray_backproject", "ray_sart", "rayPaths", "globalAverageC", "scan_convert", "scan_convert3", "demod", "resample", "resample_taps", "upfirdn", "filtfilt", "fdtd", "fdtd3", "UltrasoundSystem", "Transducer", "Sequence", "Scan", "ChannelData"]

@@ -43,6 +43,7 @@ SYMBOLS = (
     "qdas_eikonal3", "qdas_eikonal3_tables", "qdas_eikonal3_work_bytes", "qdas_eikonal3_pass_cap",
     "qdas_scanconvert", "qdas_demod", "qdas_demod_len", "qdas_resample", "qdas_resample_len", "qdas_upfirdn_len",
     "qdas_fdtd", "qdas_fdtd_tiles", "qdas_fdtd_tile_lists",
+    "qdas_fdtd3", "qdas_fdtd3_bricks", "qdas_fdtd3_brick_lists",
 )
 
 
@@ -214,6 +215,24 @@ class FdtdArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in FDTD_ARGS]
 
 
+FDTD3_TZ, FDTD3_TX, FDTD3_TY, FDTD3_ZERO = 64, 8, 8, 1
+
+
+class Fdtd3Desc(C.Structure):
+    _fields_ = [("Nz", C.c_uint64), ("Nx", C.c_uint64), ("Ny", C.c_uint64), ("V", C.c_uint64), ("Nt", C.c_uint64), ("ld", C.c_uint64), ("pstride", C.c_uint64),
+                ("vstride", C.c_uint64), ("M", C.c_uint64), ("Ts", C.c_uint64), ("N", C.c_uint64), ("rec_st", C.c_uint64), ("rec_sn", C.c_uint64),
+                ("rec_sv", C.c_uint64), ("dt_h", C.c_double), ("inv_h", C.c_double), ("dtype", C.c_int32), ("order", C.c_int32), ("device", C.c_int32),
+                ("flags", C.c_int32), ("queue", C.c_void_p)]
+
+
+FDTD3_ARGS = ("p", "uz", "ux", "uy", "rz", "rx", "ry", "c2", "rho", "dtrz", "dtrx", "dtry", "az", "azs", "ax", "axs", "ay", "ays", "s", "src_wz", "src_wx",
+              "src_wy", "src_node", "src_start", "src_list", "sen_node", "sen_start", "sen_list", "rec")
+
+
+class Fdtd3Args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in FDTD3_ARGS]
+
+
 class QdasError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libqdas error {code}: {msg}")
@@ -308,6 +327,10 @@ def lib():
     L.qdas_fdtd_tiles.argtypes = [C.c_uint64, C.c_uint64]
     L.qdas_fdtd_tiles.restype = C.c_uint64
     L.qdas_fdtd_tile_lists.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qdas_fdtd3.argtypes = [C.POINTER(Fdtd3Desc), C.POINTER(Fdtd3Args)]
+    L.qdas_fdtd3_bricks.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
+    L.qdas_fdtd3_bricks.restype = C.c_uint64
+    L.qdas_fdtd3_brick_lists.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.qdas_convd_len.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
     L.qdas_convd_len.restype = C.c_uint64
     L.qdas_shift_sum.argtypes = [C.POINTER(ShiftDesc), C.c_void_p, C.c_void_p, C.c_void_p]

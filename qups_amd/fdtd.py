@@ -37,10 +37,11 @@ def _order(order):
 
 
 def grid_spacing(z, x, y=None):
-    """``h`` of a uniform square grid; unequal or non-uniform spacing (beyond 1e-6 relative) and a non-singleton y are refused"""
+    """``h`` of a uniform square grid; unequal or non-uniform spacing (beyond 1e-6 relative) and a non-singleton y (``fdtd3.grid_spacing3`` takes volumes) are
+    refused"""
     z, x = np.asarray(z, np.float64).reshape(-1), np.asarray(x, np.float64).reshape(-1)
     if y is not None and np.size(y) > 1:
-        raise DasError("fdtd: the grid has a non-singleton y; 3-D is not built")
+        raise DasError("fdtd: the grid has a non-singleton y; this is the 2-D solver (3-D grids: qups_amd.fdtd3)")
     if z.size < 2 or x.size < 2:
         raise DasError("fdtd: the grid needs at least two nodes in z and in x")
     dz, dx = np.diff(z), np.diff(x)
@@ -102,9 +103,9 @@ def _largest_prime_factor(n):
     return max(best, n) if n > 1 else best
 
 
-def pml_size(PML, Z, X):
-    """a scalar is taken as is; a pair ``[lo, hi]`` picks the size in that range whose ``Z + 2P`` and ``X + 2P`` have the smallest largest prime factor
-    (the first such size), as the reference does for its FFTs -- harmless here, kept for parity"""
+def pml_size(PML, Z, X, Y=None):
+    """a scalar is taken as is; a pair ``[lo, hi]`` picks the size in that range whose ``Z + 2P`` and ``X + 2P`` (and ``Y + 2P`` of a volume) have the
+    smallest largest prime factor (the first such size), as the reference does for its FFTs -- harmless here, kept for parity"""
     if np.ndim(PML) == 0:
         P = int(PML)
         if P < 0 or P != PML:
@@ -115,7 +116,8 @@ def pml_size(PML, Z, X):
     lo, hi = (int(v) for v in np.asarray(PML).reshape(-1))
     if lo < 0 or hi < lo:
         raise DasError(f"fdtd: PML is a size or a range [lo, hi], got {PML!r}")
-    return min(range(lo, hi + 1), key=lambda P: (max(_largest_prime_factor(Z + 2 * P), _largest_prime_factor(X + 2 * P)), P))
+    ext = [n for n in (Z, X, Y) if n is not None]
+    return min(range(lo, hi + 1), key=lambda P: (max(_largest_prime_factor(n + 2 * P) for n in ext), P))
 
 
 def pml_factors(N, P, c_max, h, dt):

@@ -547,7 +547,8 @@ class UltrasoundSystem:
         reference's default medium, ``:2638``).  ``PML``: a size, or a range ``[lo, hi]``.  ``bsize``: pulses per solver call.  The record is ``T x N x V`` at
         ``fs_ = ratio us.fs``, as the reference returns it: the caller downsamples.  ``field=True``: the pressure of the whole interior grid per step,
         ``T x (Z X) x V`` (sensors = all nodes, ``Z`` slowest, no receive impulse), refused above 2 GiB.  ``plan_only``: the wrapper arithmetic alone, a dict
-        (no device needed).  Not built: 3-D, absorption, nonlinearity, ``'linear'`` and ``karray-*`` element mapping, sensor directivity."""
+        (no device needed).  A ``cgrd`` with three non-singleton dimensions goes to the 3-D solver (``qups_amd/fdtd3.py`` -> ``qdas_fdtd3``): ``c``, ``rho`` of
+        ``cgrd.size``, ``field`` as ``T x (Z X Y) x V``.  Not built: absorption, nonlinearity, ``'linear'`` and ``karray-*`` element mapping, sensor directivity."""
         from . import fdtd as F
         if ElemMapMethod != "nearest":
             if ElemMapMethod in ("linear", "karray-direct", "karray-depend"):
@@ -558,6 +559,9 @@ class UltrasoundSystem:
         cgrd = cgrd or self.scan
         if cgrd.axes is None or cgrd.axes.get("kind") != "cartesian":
             raise DasError("fdtdSim: cgrd must be a Cartesian scan made by Scan.cartesian (order 'ZXY').")
+        if sum(int(v) > 1 for v in tuple(cgrd.size)) == 3:           # three non-singleton dimensions -> the 3-D solver (reference :2929-2948), as in bfEikonal
+            return self._fdtdSim3(c, rho, cgrd, waveform=waveform, wv_t0=wv_t0, wv_fs=wv_fs, rx_impulse=rx_impulse, rx_t0=rx_t0, c0=c0, rho0=rho0, T=T, PML=PML,
+                                  CFL_max=CFL_max, order=order, isosub=isosub, field=field, bsize=bsize, prec=prec, plan_only=plan_only)
         z, x = cgrd.axes["z"], cgrd.axes["x"]
         h = F.grid_spacing(z, x, cgrd.axes["y"])
         Z, X = z.size, x.size
@@ -607,6 +611,62 @@ class UltrasoundSystem:
             taps = F._sample_cubic(w, np.arange(nr) / fs_ * wv_fs)
             y = convd(y, torch.from_numpy(taps).to(device=y.device, dtype=y.dtype).reshape(-1, 1, 1), 1, "full")
         return ChannelData(y, plan["t0"], fs_, "TNM")
+
+    def _fdtdSim3(self, c, rho, cgrd, *, waveform, wv_t0, wv_fs, rx_impulse, rx_t0, c0, rho0, T, PML, CFL_max, order, isosub, field, bsize, prec, plan_only):
+        """:meth:`fdtdSim` on a volume: ``c``, ``rho`` of ``cgrd.size = Z x X x Y``, through ``qups_amd/fdtd3.py`` -> ``qdas_fdtd3``.  The same wrapper contract
+        with three axes: the normals from all three rows of ``tx.normals`` (``ux``, ``uy``, ``uz``, ``:2874-2878``), ``T`` defaulting to
+        ``2 |(dx, dy, dz)| / c0`` (``:2890``), ``field=True`` as ``T x (Z X Y) x V`` with the nodes in C order of ``(Z, X, Y)``."""
+        from . import fdtd as F
+        from . import fdtd3 as F3
+        z, x, y = cgrd.axes["z"], cgrd.axes["x"], cgrd.axes["y"]
+        h = F3.grid_spacing3(z, x, y)
+        Z, X, Y = z.size, x.size, y.size
+        c0 = float(self.seq.c0 if c0 is None else c0)
+        rho0 = float(c0 / 1.5 if rho0 is None else rho0)
+        c = F3._host(c)
+        if c.size != Z * X * Y:
+            raise DasError(f"fdtdSim: c must have the grid's size Z x X x Y = {Z} x {X} x {Y}")
+        c = c.reshape(Z, X, Y)
+        rho = np.full((Z, X, Y), rho0) if rho is None else F3._host(rho)
+        if rho.size != Z * X * Y:
+            raise DasError(f"fdtdSim: rho must have the grid's size Z x X x Y = {Z} x {X} x {Y}")
+        rho = rho.reshape(Z, X, Y)
+        if self.fs is None:
+            raise DasError("fdtdSim: the system needs a sampling frequency fs")
+        ratio, fs_, dt = F.time_step(self.fs, c.max(), h, CFL_max, order)
+        F3._check_step(c.max(), dt, h, int(order) // 2)
+        s, txn0, txne = F.tx_table(waveform, wv_t0, wv_fs, self.seq.delays(self.tx), self.seq.apodization(self.tx), fs_)
+        if T is None:
+            T = 2.0 * math.sqrt((x[-1] - x[0]) ** 2 + (y[-1] - y[0]) ** 2 + (z[-1] - z[0]) ** 2) / c0
+        Nt = 1 + int(math.floor((float(T) + (txne - txn0) / fs_) * fs_ + 1e-9))
+        P = F.pml_size(PML, Z, X, Y)
+        rx_t0 = float(rx_t0) if (rx_impulse is not None and not field) else 0.0
+        plan = dict(h=h, ratio=ratio, fs_=fs_, dt=dt, txn0=txn0, txne=txne, Nt=Nt, t0=txn0 / fs_ + rx_t0, P=P, Nz=Z + 2 * P, Nx=X + 2 * P, Ny=Y + 2 * P,
+                    T=float(T), rho=rho, rho_iso=F.iso_density(c, c0, rho0) if isosub else None)
+        nrm = np.stack([self.tx.normals[2], self.tx.normals[0], self.tx.normals[1]])
+        V = s.shape[2]
+        if field:
+            sen, sen_nodes = np.zeros((3, 0)), tuple(np.indices((Z, X, Y)).reshape(3, -1))   # every node, C order of (Z, X, Y): no search
+            if Nt * Z * X * Y * V * (4 if prec == "single" else 8) > 2 ** 31:
+                raise DasError(f"fdtdSim: field=True would return {Nt} x {Z * X * Y} x {V} values, above 2 GiB; shorten T or coarsen the grid")
+        else:
+            sen, sen_nodes = self.rx.positions(), None
+        src_nodes = F3.nearest_nodes3(z, x, y, self.tx.positions())       # (raises the reference's assertion before any device work)
+        plan.update(src_nodes=src_nodes, sen_nodes=F3.nearest_nodes3(z, x, y, sen) if not field else None)
+        if plan_only:
+            return plan
+        run = lambda r: F3.fdtd3(c, r, z, x, y, self.tx.positions(), nrm, s, sen, Nt, dt, PML=P, order=order, prec=prec, bsize=bsize, sen_nodes=sen_nodes)
+        yd = run(rho)
+        if isosub:
+            yd = yd - run(plan["rho_iso"])
+        if rx_impulse is not None and not field:
+            import torch
+            from .convd import convd
+            w = np.asarray(rx_impulse, np.float64).reshape(-1)
+            nr = int(math.floor((w.size - 1) / wv_fs * fs_ + 1e-9)) + 1
+            taps = F._sample_cubic(w, np.arange(nr) / fs_ * wv_fs)
+            yd = convd(yd, torch.from_numpy(taps).to(device=yd.device, dtype=yd.dtype).reshape(-1, 1, 1), 1, "full")
+        return ChannelData(yd, plan["t0"], fs_, "TNM")
 
     def _num_tx(self, chd):
         return int(chd.data.shape[chd.order.index("M")])

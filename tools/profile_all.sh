@@ -95,6 +95,7 @@ python tools/raybackproject_time.py > profiles/raybackproject_time.txt 2>/dev/nu
 python tools/demod_time.py > profiles/demod_time.txt 2>/dev/null
 python tools/resample_time.py > profiles/resample_time.txt 2>/dev/null
 python tools/fdtd_time.py > profiles/fdtd_time.txt 2>/dev/null
+python tools/fdtd3_time.py > profiles/fdtd3_time.txt 2>/dev/null
 # ---- PCIe-inclusive: host-resident frames through the C ABI, and the int16 RF -> hilbert -> band-pass -> DAS chain for a stream
 python tools/host_frames.py > $OUT/host_frames.txt 2>/dev/null
 python tools/pipeline_bench.py c3 12 64 > $OUT/pipeline_bench.txt 2>/dev/null; python tools/pipeline_bench.py c2 12 64 >> $OUT/pipeline_bench.txt 2>/dev/null
