@@ -889,6 +889,30 @@ uint64_t qdas_fdtd_tiles(uint64_t Nz, uint64_t Nx);      /* ceil(Nz / TZ) ceil(N
 int qdas_fdtd_tile_lists(uint64_t Nz, uint64_t Nx, uint64_t n, const int32_t *node, int32_t *start, int32_t *list);
 int qdas_fdtd(const qdas_fdtd_desc *d, const qdas_fdtd_args *a);
 
+/* ---- qdas_fdtd with power-law absorption: the scheme, the descriptor, the argument block and every rule of qdas_fdtd, with step 4 replaced.  A relaxation
+ * FDTD of the Fullwave kind (memory variables), NOT k-Wave's fractional Laplacian.  With rn = rz + rx after step 3:
+ *   QDAS_FDTD_LOSS_RELAX  (1 <= y < 2, L = 1 .. 4 mechanisms):   e_l <- e_l + E[l] (rn - e_l),   p = c2 (rn + kap sum_l g[l] (rn - e_l))   (the updated e_l)
+ *   QDAS_FDTD_LOSS_STOKES (y = 2, L = 0, no extra state):        p = c2 (rn + kap (rn - ro)),    ro = rz + rx before step 3
+ * and p = c2 rn exactly where kap is 0.  kap is an Nx x Nz dense map like the medium's: 2 c a under relaxation (a in Np (rad/s)^-y m^-1), mud = 2 c a / dt
+ * under Stokes.  E[l] = 1 - exp(-dt / tau_l); for small loss alpha(w) = (w / 2c) kap sum_l g[l] (-Im D_l(w)) with the update's own discrete response
+ * D_l = 1 - E_l / (1 - (1 - E_l) e^{i w dt}) (qups_amd/fdtd.py relaxation_fit makes tau, E, g); Stokes gives a w^2 less the (w dt)^2 / 6 of its backward
+ * difference.  The unrelaxed speed c sqrt(1 + kap sum g) is what the caller's time step must respect.
+ * e holds the memory variables, in the states' type and layout: mechanism l of pulse v starts at (v L + l) vstride, rows of ld.  QDAS_FDTD_ZERO clears e too.
+ * Still two launches per step (the velocity pass is qdas_fdtd's kernel), no atomics, two runs give the same bits, pulses never mix.
+ * Validation, on the host before any HIP call: every row of qdas_fdtd, and a null loss block, an unknown mode, L > 4, L = 0 with RELAX or L > 0 with STOKES,
+ * a g that is not finite or negative, an E outside (0, 1], and -- for a call that has work -- a null kap, or a null e with L > 0: QDAS_EINVAL.  Nt = 0 or
+ * V = 0: QDAS_OK, nothing is launched. */
+#define QDAS_FDTD_LOSS_STOKES 1
+#define QDAS_FDTD_LOSS_RELAX 2
+#define QDAS_FDTD_MAX_L 4
+typedef struct qdas_fdtd_loss {
+    int32_t mode, L;                   /* QDAS_FDTD_LOSS_STOKES (L = 0) | QDAS_FDTD_LOSS_RELAX (L = 1 .. 4) */
+    double g[4], E[4];                 /* weights and 1 - exp(-dt / tau_l) of the mechanisms 0 .. L-1         */
+    const void *kap;                   /* Nx x Nz: 2 c a (RELAX) or 2 c a / dt (STOKES)                        */
+    void *e;                           /* V L arrays of the states' layout, updated in place                   */
+} qdas_fdtd_loss;
+int qdas_fdtd_lossy(const qdas_fdtd_desc *d, const qdas_fdtd_args *a, const qdas_fdtd_loss *l);
+
 /* ---- 3-D acoustic FDTD (fdtd3.hip): the scheme of qdas_fdtd with a third axis -- linear, lossless, first order in time, of order 2R in space (R = 1, 2, 4)
  * on a staggered grid -- for channel data through volumes (the reference's kspaceFirstOrder picks kspaceFirstOrder3D for a grid of three dimensions,
  * src/UltrasoundSystem.m:2929-2948).  FDTD, NOT k-space pseudospectral.

@@ -81,6 +81,8 @@
  *         rational-rate polyphase FIR: resample, upfirdn, FIR filtfilt; described at cmd_resample below.
  *   rec     = qdas_mex('fdtd', med, pml, s, src, sen, [Nz Nx V Nt dt_h inv_h order])
  *         2-D acoustic FDTD from rest, the record of the sensors; described at cmd_fdtd below.
+ *   rec     = qdas_mex('fdtdloss', med, pml, s, src, sen, [Nz Nx V Nt dt_h inv_h order], kap, [mode g E])
+ *         the same with power-law absorption (qdas_fdtd_lossy); described at cmd_fdtd below.
  *   rec     = qdas_mex('fdtd3', med, pml, s, src, sen, [Nz Nx Ny V Nt dt_h inv_h order])
  *         the same through a volume; described at cmd_fdtd3 below.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
@@ -1245,9 +1247,13 @@ static mxArray *cmd_resample(int nrhs, const mxArray *prhs[]) {
  * source [node; wz; wx] with node = j Nz + i (0-based) and wz = nz 2 c dt / h.  sen: N host values, the sensors' nodes (0-based).
  * prm = [Nz Nx V Nt dt_h inv_h order], order 2, 4 or 8 (optional, default 8).  rec: Nt x N x V of the class of med (time first, as ChannelData holds it).
  * The states are the gateway's own scratch, cleared on the device (QDAS_FDTD_ZERO); sources and sensors must sit on distinct nodes.  M = 0 (src empty) is
- * allowed: the record is then all zeros. */
-static mxArray *cmd_fdtd(int nrhs, const mxArray *prhs[]) {
-    if (nrhs != 6) mexErrMsgIdAndTxt("QUPS:das_spec:nargin", "qdas_mex('fdtd', med, pml, s, src, sen, prm)");
+ * allowed: the record is then all zeros.
+ * rec = qdas_mex('fdtdloss', med, pml, s, src, sen, prm, kap, loss) -- the same with absorption (qdas_fdtd_lossy).  kap: Nz x Nx of the class of med, the loss
+ * map extended like the medium (2 c a under relaxation, 2 c a / dt under Stokes; qups_amd/fdtd.py `loss_model` is the recipe).  loss: host values
+ * [mode g(1 .. L) E(1 .. L)], mode 1 = Stokes (L = 0) | 2 = relaxation (L = 1 .. 4).  The L memory variables per pulse are scratch of the call like the states. */
+static mxArray *cmd_fdtd(int nrhs, const mxArray *prhs[], int lossy) {
+    if (nrhs != (lossy ? 8 : 6))
+        mexErrMsgIdAndTxt("QUPS:das_spec:nargin", lossy ? "qdas_mex('fdtdloss', med, pml, s, src, sen, prm, kap, loss)" : "qdas_mex('fdtd', med, pml, s, src, sen, prm)");
     const mxClassID cls = mxGetClassID(prhs[0]);
     if ((cls != mxDOUBLE_CLASS && cls != mxSINGLE_CLASS) || mxIsComplex(prhs[0])) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtd: med must be real single or double.");
     if (mxGetClassID(prhs[1]) != cls || mxGetClassID(prhs[2]) != cls || mxIsComplex(prhs[1]) || mxIsComplex(prhs[2]))
@@ -1274,9 +1280,24 @@ static mxArray *cmd_fdtd(int nrhs, const mxArray *prhs[]) {
     d.Ts = MV ? ns / MV : 0;
     if (MV ? ns % MV != 0 : ns != 0) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtd: s holds %llu values, not V x M x T' with V = %llu, M = %llu.", (unsigned long long)ns, (unsigned long long)d.V, (unsigned long long)d.M);
     d.rec_st = 1; d.rec_sn = d.Nt; d.rec_sv = d.Nt * d.N;
+    qdas_fdtd_loss q;
+    memset(&q, 0, sizeof q);
+    if (lossy) {
+        if (mxGetClassID(prhs[6]) != cls || mxIsComplex(prhs[6]) || mxGetNumberOfElements(prhs[6]) != cells)
+            mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtdloss: kap must be Nz x Nx, real and of the class of med.");
+        const size_t nl = mxGetNumberOfElements(prhs[7]);
+        if (nl < 1 || nl % 2 != 1 || nl > 1 + 2 * QDAS_FDTD_MAX_L) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtdloss: loss = [mode g(1 .. L) E(1 .. L)] with L <= 4.");
+        const double mn = num_at(prhs[7], 0, "loss");
+        q.mode = (mn == floor(mn) && fabs(mn) < 1e6) ? (int32_t)mn : -1;
+        q.L = (int32_t)(nl / 2);
+        for (int k = 0; k < q.L; ++k) { q.g[k] = num_at(prhs[7], (mwSize)(1 + k), "loss"); q.E[k] = num_at(prhs[7], (mwSize)(1 + q.L + k), "loss"); }
+    }
     const mwSize dims[3] = {(mwSize)d.Nt, (mwSize)d.N, (mwSize)d.V};
     if (d.Nt * d.V == 0 || d.N == 0) {
-        const int rc = d.N == 0 ? QDAS_OK : qdas_fdtd(&d, NULL);                                      /* (an empty call is still validated) */
+        const uint64_t keep = d.Nt;
+        if (d.N == 0) d.Nt = 0;                                                                       /* no sensors: nothing to run, but the call is still validated */
+        const int rc = lossy ? qdas_fdtd_lossy(&d, NULL, &q) : (d.N == 0 ? QDAS_OK : qdas_fdtd(&d, NULL));
+        d.Nt = keep;
         if (rc) CFAIL("%s", qdas_last_error());
         release_devargs();
         return mxCreateNumericArray(3, dims, cls, mxREAL);
@@ -1307,7 +1328,7 @@ static mxArray *cmd_fdtd(int nrhs, const mxArray *prhs[]) {
         free(hi); free(hr);
         CFAIL("fdtd: the nodes of src and sen are integers in [0, Nz Nx).");
     }
-    const size_t sbytes = 5 * cells * (size_t)d.V * rs;
+    const size_t sbytes = (size_t)(5 + q.L) * cells * (size_t)d.V * rs;                                 /* the five states, then the V L memory variables */
     char *di = (char *)dev_extra(ni * sizeof(int32_t)), *dr = (char *)dev_extra((nr ? nr : 1) * rs), *ds = (char *)dev_extra(sbytes);
     int rc = qdas_device_copy(di, hi, ni * sizeof(int32_t), 0, -1);
     if (!rc && nr) rc = qdas_device_copy(dr, hr, nr * rs, 0, -1);
@@ -1327,8 +1348,12 @@ static mxArray *cmd_fdtd(int nrhs, const mxArray *prhs[]) {
     a.src_node = dii; a.src_start = dii + d.M; a.src_list = a.src_start + nt + 1; a.sen_node = a.src_list + d.M; a.sen_start = a.sen_node + d.N; a.sen_list = a.sen_start + nt + 1;
     const size_t bytes = (size_t)(d.Nt * d.N * d.V) * rs;
     mxArray *host;
+    if (lossy) {
+        q.kap = dev_in(prhs[6], cells * rs, "kap", &dev);
+        q.e = q.L ? ds + 5 * sb : NULL;
+    }
     a.rec = dev_out(3, dims, cls, 0, dev, bytes, &host);
-    return finish(qdas_fdtd(&d, &a), host, bytes);
+    return finish(lossy ? qdas_fdtd_lossy(&d, &a, &q) : qdas_fdtd(&d, &a), host, bytes);
 }
 
 /* rec = qdas_mex('fdtd3', med, pml, s, src, sen, prm) -- Nt steps of the 3-D acoustic FDTD scheme (qdas_fdtd3, include/qdas.h) from rest, on tables the caller
@@ -1479,7 +1504,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "scanconvert")) { plhs[0] = cmd_scanconvert(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "demod")) { plhs[0] = cmd_demod(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "resample")) { plhs[0] = cmd_resample(nrhs - 1, prhs + 1);
-        } else if (!strcmp(cmd, "fdtd")) { plhs[0] = cmd_fdtd(nrhs - 1, prhs + 1);
+        } else if (!strcmp(cmd, "fdtd")) { plhs[0] = cmd_fdtd(nrhs - 1, prhs + 1, 0);
+        } else if (!strcmp(cmd, "fdtdloss")) { plhs[0] = cmd_fdtd(nrhs - 1, prhs + 1, 1);
         } else if (!strcmp(cmd, "fdtd3")) { plhs[0] = cmd_fdtd3(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();

@@ -11,7 +11,8 @@
 //   3. rz <- az (az rz - dt rho D-z uz),  rx <- ax (ax rx - dt rho D-x ux)
 //   4. p = c2 (rz + rx)
 //   5. rec[n, j, v] = p[sensor j]
-// Steps 1-2 are the velocity pass, 3-5 the density pass.
+// Steps 1-2 are the velocity pass, 3-5 the density pass.  With absorption (qdas_fdtd_lossy) step 4 is density_cells_lossy's; every other step is the same
+// text (tests/fdtd_loss_core_host.cpp walks it).
 //
 // THE TILE.  A workgroup of LANES = 256 lanes owns TZ x TX = 64 x 16 nodes of one pulse: lane t has z offset t mod 64 (a wave is one contiguous row of 64) and
 // the rows (t div 64) + 4 r, r = 0 .. 3.  The velocity pass stages p with a halo of R on every side ((TZ + 2R) x (TX + 2R) words); the density pass stages uz
@@ -29,6 +30,13 @@
 #else
 #define QDAS_FD_HD inline
 #define QDAS_FD_UNROLL
+#endif
+// QDAS_FD_ROUNDED(x): x is a rounded value of its own from here on -- the device compiler may not fold the product that made it into a later sum as an FMA
+// (an empty statement that claims to modify x; nothing on the host, which is built without contraction).  density_cells_lossy needs it: see there.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define QDAS_FD_ROUNDED(x) asm volatile("" : "+v"(x))
+#else
+#define QDAS_FD_ROUNDED(x) ((void)0)
 #endif
 
 namespace qdas {
@@ -153,6 +161,80 @@ QDAS_FD_UNROLL
         rz[o] = vz;
         rx[o] = vx;
         p[o] = P.c2[m] * (vz + vx);
+    }
+}
+
+// the loss block of qdas_fdtd_lossy: `kap` is Nx x Nz dense like the medium maps (2 c a under relaxation, mud = 2 c a / dt under Stokes); mechanism l of
+// pulse v keeps its memory variable at e + (v L + l) vs, laid out like a state array
+template <typename T>
+struct Loss {
+    const T *kap;
+    T *e;
+    T g[4], E[4];
+};
+
+// THE ROUNDINGS OF THE LOSSY PASS are written out, not left to the compiler.  Built with contraction, the lossless density kernels round steps 3 and 4 in
+// one definite way (read from their code objects):
+//   d  = fma(a_R, g_R, ... fma(a_1, g_1, 0))                     the derivative sum, every product fused into it
+//   v  = A * fma(A, r, -(w * d))                                  w d and A (...) are products of their own
+//   rz + rx = vz + vx in float, fma(az, fma(az, rz, -(w dz)), vx) in double
+// and a second kernel with more arithmetic behind the same text is free to fuse differently (it did).  With a zero loss map the lossy pass must give the BITS
+// of the lossless one (tests/test_gpu_fdtd_loss.py), so it states these roundings with explicit fused operations and QDAS_FD_ROUNDED, and the compiler has
+// no choice left.  On the host the same text gives the same values.
+QDAS_FD_HD float fused(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+QDAS_FD_HD double fused(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+template <int R, typename T>
+QDAS_FD_HD T dminus_fused(const T *g, int st) {
+    T d = T(0);
+QDAS_FD_UNROLL
+    for (int k = 1; k <= R; ++k) d = fused(coef<R, T>(k), g[(k - 1) * st] - g[-k * st], d);
+    return d;
+}
+
+// steps 3 and 4 with absorption for the nodes of lane t; e: the pulse's first memory variable (unused for L = 0).  rn = rz + rx (the new ones), then
+//   L = 0 (Stokes):      p = c2 (rn + mud (rn - ro)),                      ro = rz + rx before the update
+//   L > 0 (relaxation):  e_l <- e_l + E_l (rn - e_l),  p = c2 (rn + kap sum_l g_l (rn - e_l))
+// and p = c2 rn where the map is 0.  The memory variables are updated at every node, lossy or not.
+template <int R, typename T, int L>
+QDAS_FD_HD void density_cells_lossy(const Params<T> &P, const Loss<T> &Q, const T *lz, const T *lx, T *rz, T *rx, T *p, T *e, int i0, int j0, int t) {
+    constexpr int W = TZ + 2 * R;
+    const int tz = t % TZ, i = i0 + tz;
+    if (i >= P.Nz) return;
+    const T a = P.az[i];
+QDAS_FD_UNROLL
+    for (int r = 0; r < PER_LANE; ++r) {
+        const int jl = t / TZ + r * ROWS, j = j0 + jl;
+        if (j >= P.Nx) break;
+        const int64_t o = (int64_t)j * P.ld + i, m = (int64_t)j * P.Nz + i;
+        const T b = P.ax[j], w = P.dt_h * P.rho[m];
+        const T oz = rz[o], ox = rx[o];
+        T wdz = w * dminus_fused<R, T>(lz + jl * W + (tz + R), 1), wdx = w * dminus_fused<R, T>(lx + (jl + R) * TZ + tz, TZ);
+        QDAS_FD_ROUNDED(wdz);
+        QDAS_FD_ROUNDED(wdx);
+        const T iz = fused(a, oz, -wdz), ix = fused(b, ox, -wdx);
+        T vz = a * iz, vx = b * ix;
+        QDAS_FD_ROUNDED(vz);
+        QDAS_FD_ROUNDED(vx);
+        rz[o] = vz;
+        rx[o] = vx;
+        T rn = sizeof(T) == 4 ? vz + vx : fused(a, iz, vx);
+        QDAS_FD_ROUNDED(rn);
+        T acc;
+        if (L == 0) {
+            acc = rn - (oz + ox);
+        } else {
+            acc = T(0);
+QDAS_FD_UNROLL
+            for (int l = 0; l < L; ++l) {
+                T *el = e + (int64_t)l * P.vs + o;
+                const T en = *el + Q.E[l] * (rn - *el);
+                *el = en;
+                acc += Q.g[l] * (rn - en);
+            }
+        }
+        const T k = Q.kap[m];
+        p[o] = P.c2[m] * (k != T(0) ? rn + k * acc : rn);      // a node without loss is step 4 itself, the sign of a zero included
     }
 }
 

@@ -5,6 +5,10 @@ its numpy restatement).  It follows the wrapper contract of the reference's ``ks
 is about our objects -- grid, time step, sources, sensors, ``t0``, ``isosub``, ``field`` -- but the numerical method is FDTD, NOT k-space pseudospectral:
 absolute amplitude and dispersion are this discretisation's and are not matched to k-Wave.
 
+Absorption is optional (``alpha``, ``alpha_power``): relaxation mechanisms fitted to a power law inside a band (:func:`relaxation_fit`), or the Stokes
+term at ``alpha_power = 2`` -- a relaxation FDTD of the Fullwave kind, NOT k-Wave's fractional Laplacian (``qdas_fdtd_lossy``;
+``tests/fdtd_loss_ref.py`` is its restatement).  Without ``alpha`` the solver is lossless and takes the path it always took.
+
 Everything the kernel reads is prepared here on the host in float64 (the extended medium, staggered densities, PML factors, the sampled source table, the
 per-tile point lists) and uploaded once; the states, the record and every table are torch tensors, so the C entry allocates nothing.  There is no CPU
 fallback: without the library or a device the call raises."""
@@ -19,7 +23,7 @@ from . import _lib
 from .das_spec import DasError
 
 __all__ = ["fdtd", "launch", "prepare", "time_step", "stability_limit", "tx_table", "pml_size", "pml_factors", "nearest_nodes", "iso_density", "grid_spacing",
-           "tile_lists", "COEFS", "TILE", "STATES"]
+           "tile_lists", "COEFS", "TILE", "STATES", "relaxation_fit", "relaxation_response", "alpha_np", "loss_model", "loss_time_step", "FIT_SPREADS"]
 
 COEFS = {1: (1.0,), 2: (9.0 / 8.0, -1.0 / 24.0), 4: (1225.0 / 1024.0, -245.0 / 3072.0, 49.0 / 5120.0, -5.0 / 7168.0)}
 TILE = (_lib.FDTD_TZ, _lib.FDTD_TX)
@@ -162,6 +166,132 @@ def tile_lists(Nz, Nx, nodes):
     return start, lst[:nodes.size]
 
 
+FIT_SPREADS = (1.0, 1.5, 2.0, 3.0, 4.0, 6.0)      # the `s` of relaxation_fit: how far the centres reach past the band
+FIT_POINTS = 64
+
+
+def alpha_np(alpha, y):
+    """``a`` in Np (rad/s)^-y m^-1 from ``alpha`` in dB/(MHz^y cm), k-Wave's unit (the reference hands ``1e4 Medium.alpha0`` to k-Wave in it,
+    ``src/Medium.m:443``): ``a = alpha 100 / (20 log10 e) (1e-6 / 2 pi)^y``"""
+    return np.asarray(alpha, np.float64) * 100.0 / (20.0 * math.log10(math.e)) * (1e-6 / (2.0 * math.pi)) ** float(y)
+
+
+def relaxation_response(tau, dt, w):
+    """``(E, D)``: ``E_l = 1 - exp(-dt / tau_l)`` and the DISCRETE response ``D_l(w) = 1 - E_l / (1 - (1 - E_l) e^{i w dt})`` of the update
+    ``e <- e + E (r - e)`` (``r - e = D r``), ``L x len(w)`` complex.  Its limit for ``dt -> 0`` is the Debye response ``-i w tau / (1 - i w tau)``."""
+    tau = np.asarray(tau, np.float64).reshape(-1)
+    w = np.asarray(w, np.float64).reshape(-1)
+    E = -np.expm1(-float(dt) / tau)
+    D = 1.0 - E[:, None] / (1.0 - (1.0 - E[:, None]) * np.exp(1j * w[None] * float(dt)))
+    return E, D
+
+
+def _nnls_active_sets(A, b):
+    """``min |A g - b|_2`` over ``g >= 0`` for a handful of columns: the least-squares solution of every subset of columns that comes out positive is a
+    candidate, and the optimum is the best of them (it is the unconstrained solution on its own support)"""
+    n = A.shape[1]
+    best, best_r = np.zeros(n), float(np.linalg.norm(b))
+    for mask in range(1, 1 << n):
+        cols = [k for k in range(n) if mask >> k & 1]
+        g, *_ = np.linalg.lstsq(A[:, cols], b, rcond=None)
+        if not (g > 0).all():
+            continue
+        r = float(np.linalg.norm(A[:, cols] @ g - b))
+        if r < best_r:
+            best_r, best = r, np.zeros(n)
+            best[cols] = g
+    return best
+
+
+def relaxation_fit(y, band, dt, L=3):
+    """``(tau, E, g, fit_err)``: ``L`` relaxation mechanisms whose summed loss follows ``w^y`` over ``band = (f_lo, f_hi)`` at the time step ``dt``.
+
+    For small loss the scheme absorbs ``alpha(w) = (w / 2c) kap sum_l g_l (-Im D_l(w))`` with the update's own discrete response ``D_l``
+    (:func:`relaxation_response`), so with ``kap = 2 c a`` the weights must make ``sum_l g_l (-Im D_l(w)) = w^(y - 1)``.  The centres ``1 / (2 pi tau_l)`` are
+    log-spaced over ``[f_lo / s, s f_hi]``; for each ``s`` of ``FIT_SPREADS`` the non-negative ``g`` minimises the least squares of
+    ``sum_l g_l (-Im D_l(w)) / w^(y - 1) - 1`` over 64 log-spaced frequencies of the band (the ``2^L`` active sets, each a ``lstsq``), and the ``s`` with the
+    smallest LARGEST deviation is kept.  ``fit_err`` is that largest relative deviation from the power law inside the band: the model's own error, before
+    any discretisation in space.  float64, numpy only."""
+    y, dt, L = float(y), float(dt), int(L)
+    f_lo, f_hi = (float(v) for v in band)
+    if not 1 <= L <= _lib.FDTD_MAX_L:
+        raise ValueError(f"relaxation_fit: L is 1 .. {_lib.FDTD_MAX_L}, got {L}")
+    if not (0 < f_lo < f_hi and math.isfinite(f_hi)):
+        raise ValueError(f"relaxation_fit: the band is (f_lo, f_hi) with 0 < f_lo < f_hi, got {band!r}")
+    if not (1.0 <= y < 2.0):
+        raise ValueError(f"relaxation_fit: 1 <= y < 2 (y = 2 is the Stokes term), got {y}")
+    if not dt > 0:
+        raise ValueError("relaxation_fit: dt must be positive")
+    w = 2.0 * math.pi * np.geomspace(f_lo, f_hi, FIT_POINTS)
+    w_ref = 2.0 * math.pi * math.sqrt(f_lo * f_hi)
+    best = None
+    for s in FIT_SPREADS:
+        fc = np.geomspace(f_lo / s, s * f_hi, L) if L > 1 else np.array([math.sqrt(f_lo * f_hi)])
+        tau = 1.0 / (2.0 * math.pi * fc)
+        E, D = relaxation_response(tau, dt, w)
+        A = (-D.imag / (w[None] / w_ref) ** (y - 1.0)).T           # columns scaled to O(1): g = g' w_ref^(y - 1)
+        g = _nnls_active_sets(A, np.ones(w.size))
+        err = float(np.abs(A @ g - 1.0).max())
+        if best is None or err < best[3]:
+            best = (tau, E, g * w_ref ** (y - 1.0), err)
+        if L == 1:
+            break                                                    # one centre: the spread does not move it
+    return best
+
+
+def loss_model(c, alpha, alpha_power, alpha_band, dt, mechanisms=3):
+    """the loss block of one run from the interior maps, float64: a dict with ``mode`` (``"stokes"`` | ``"relax"``), ``L``, ``tau, E, g, fit_err`` and
+    ``kap`` (``Z x X``: ``2 c a`` under relaxation, ``mud = 2 c a / dt`` under Stokes), and ``speed``: the largest speed the time step must respect,
+    ``max c sqrt(1 + kap sum g)`` (the unrelaxed speed) or, for Stokes, ``max c sqrt(1 + 2 mud)`` (its factor at the Nyquist frequency).  ``alpha``: a scalar
+    or a ``Z x X`` map in dB/(MHz^y cm); ``y < 1``, ``y > 2`` and a negative or non-finite ``alpha`` raise ``ValueError``."""
+    c = np.asarray(c, np.float64)
+    y = 1.01 if alpha_power is None else float(alpha_power)
+    if not (1.0 <= y <= 2.0):
+        raise ValueError(f"fdtd: alpha_power is 1 .. 2 (relaxation below 2, Stokes at 2), got {alpha_power!r}")
+    al = np.asarray(alpha.detach().cpu().numpy() if hasattr(alpha, "detach") else alpha, np.float64)
+    if al.ndim and al.size != c.size:
+        raise DasError(f"fdtd: alpha is a scalar or a map of the grid's size {c.shape}, got {al.shape}")
+    if not np.isfinite(al).all() or (al < 0).any():
+        raise ValueError("fdtd: alpha must be finite and not negative")
+    a = alpha_np(np.broadcast_to(al.reshape(c.shape) if al.ndim else al, c.shape), y)
+    dt = float(dt)
+    if y == 2.0:
+        kap = 2.0 * c * a / dt
+        return dict(mode="stokes", L=0, y=y, tau=np.zeros(0), E=np.zeros(0), g=np.zeros(0), fit_err=0.0, kap=kap, speed=float((c * np.sqrt(1.0 + 2.0 * kap)).max()))
+    if alpha_band is None:
+        raise DasError("fdtd: alpha_band = (f_lo, f_hi) is needed to fit the relaxation mechanisms")
+    tau, E, g, fit_err = relaxation_fit(y, alpha_band, dt, mechanisms)
+    kap = 2.0 * c * a
+    return dict(mode="relax", L=int(mechanisms), y=y, tau=tau, E=E, g=g, fit_err=fit_err, kap=kap, speed=float((c * np.sqrt(1.0 + kap * g.sum())).max()))
+
+
+def _given_loss(loss, c):
+    """a caller's loss block checked and completed to :func:`loss_model`'s dict"""
+    mode = loss.get("mode")
+    if mode not in ("stokes", "relax"):
+        raise DasError(f"fdtd: the loss block's mode is 'stokes' or 'relax', got {mode!r}")
+    g, E = (np.asarray(loss.get(k, ()), np.float64).reshape(-1) for k in ("g", "E"))
+    kap = np.asarray(loss["kap"], np.float64)
+    if kap.shape != c.shape:
+        raise DasError(f"fdtd: the loss map has the grid's size {c.shape}, got {kap.shape}")
+    if g.size != E.size or (mode == "stokes") != (g.size == 0) or g.size > _lib.FDTD_MAX_L:
+        raise DasError(f"fdtd: relaxation takes 1 .. {_lib.FDTD_MAX_L} pairs (g, E), Stokes none; got {g.size} and {E.size}")
+    if not np.isfinite(kap).all() or (kap < 0).any() or not np.isfinite(g).all() or (g < 0).any() or not ((E > 0) & (E <= 1)).all():
+        raise ValueError("fdtd: the loss map and g must be finite and not negative, E inside (0, 1]")
+    speed = float((c * np.sqrt(1.0 + (2.0 * kap if mode == "stokes" else kap * g.sum()))).max())
+    return dict(mode=mode, L=int(g.size), y=loss.get("y"), tau=loss.get("tau"), E=E, g=g, fit_err=loss.get("fit_err"), kap=kap, speed=speed)
+
+
+def loss_time_step(fs, c, alpha, alpha_power, alpha_band, h, CFL_max=0.25, order=8, mechanisms=3):
+    """``(ratio, fs_, dt, loss)`` with absorption: fit at the lossless ``dt``, take ``dt`` from ``CFL_max`` with the speed bound of that fit
+    (:func:`loss_model`'s ``speed``), then fit again at the final ``dt``: ``loss`` is that last model"""
+    c = np.asarray(c, np.float64)
+    _, _, dt0 = time_step(fs, c.max(), h, CFL_max, order)
+    first = loss_model(c, alpha, alpha_power, alpha_band, dt0, mechanisms)
+    ratio, fs_, dt = time_step(fs, first["speed"], h, CFL_max, order)
+    return ratio, fs_, dt, loss_model(c, alpha, alpha_power, alpha_band, dt, mechanisms)
+
+
 def prepare(c, rho, h, dt, P):
     """the kernel's host tables in float64 from the interior medium ``c``, ``rho`` (``Z x X``): a dict with ``Nz, Nx, c2, rho, dtrz, dtrx`` (``Nx x Nz``, z
     fastest: extended by edge replication, the staggered density the mean of the two neighbours with the last row kept) and ``az, azs, ax, axs``"""
@@ -183,14 +313,23 @@ def prepare(c, rho, h, dt, P):
 
 
 def fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt, PML=20, order=8, prec="single", bsize=None, device=None, return_state=False, ld=None, prepare_only=False,
-         sen_nodes=None):
+         sen_nodes=None, alpha=None, alpha_power=None, alpha_band=None, mechanisms=3, loss=None):
     """``rec = fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt)``: ``Nt`` steps of the scheme on the grid ``z`` x ``x`` (``c``, ``rho``: ``Z x X``)
     with ``PML`` cells added on every side.  ``src_pos`` / ``sen_pos``: positions (``3 x M`` rows x, y, z, or ``2 x M`` rows z, x) mapped to their nearest
     nodes; ``src_normal``: ``2 x M`` rows ``(nz, nx)``; ``s``: the source table ``T' x M x V`` (host array or tensor).  Returns the record ``Nt x N x V`` (a
     device tensor of ``prec``), and with ``return_state`` also a dict of the five state arrays ``V x Nx x Nz`` after the last step.  ``sen_nodes``: the
     sensors' interior nodes ``(iz, ix)`` given directly, in place of ``sen_pos`` (``field``: every node).  ``bsize``: pulses per call, to bound the memory of
     the states: without ``return_state`` ONE set of ``bsize x Nx x ld`` state arrays serves every block.  ``ld``: the row stride of the state arrays (default ``Nz``).  ``prepare_only``: ``(meta, tables, s)`` on the device for :func:`launch`, nothing run.
-    Queued on torch's current stream."""
+    Queued on torch's current stream.
+
+    ABSORPTION.  ``alpha``: a scalar or a ``Z x X`` map in dB/(MHz^y cm) (k-Wave's ``alpha_coeff``), ``alpha_power = y`` (default 1.01) one number for the
+    grid.  ``1 <= y < 2``: ``mechanisms = L <= 4`` relaxation mechanisms fitted to ``w^y`` over ``alpha_band = (f_lo, f_hi)`` by :func:`relaxation_fit` at
+    this ``dt`` (a relaxation FDTD of the Fullwave kind, NOT k-Wave's fractional Laplacian; the fit's own error is ``meta["loss"]["fit_err"]`` of
+    ``prepare_only``); ``y = 2``: the Stokes term, no extra state.  The map is extended into the PML like ``c`` and ``rho``.  Each pulse then holds ``5 + L``
+    state arrays (``bsize`` bounds all of them), and ``return_state`` adds ``"e"``: ``V x L x Nx x Nz``.  ``dt`` must respect the unrelaxed speed
+    (:func:`loss_model`).  ``loss``: the block given directly in place of ``alpha`` -- a dict with ``mode`` (``"stokes"`` | ``"relax"``), ``g``, ``E`` and the
+    interior map ``kap`` (``2 c a``, or ``mud`` under Stokes), as :func:`loss_model` returns it.  ``alpha=None`` and ``loss=None``: the lossless solver,
+    exactly as before."""
     import torch
     if prec not in ("single", "double"):
         raise DasError("fdtd: prec must be 'single' or 'double'")
@@ -207,6 +346,16 @@ def fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt, PML=20, order=8,
         raise DasError("fdtd: dt must be positive")
     if c.max() * dt / h > stability_limit(R):
         raise DasError(f"fdtd: c_max dt / h = {c.max() * dt / h:.4f} is above the stability limit {stability_limit(R):.4f} of order {2 * R}")
+    if alpha is not None and loss is not None:
+        raise DasError("fdtd: give alpha or a ready-made loss block, not both")
+    if loss is not None:
+        loss = _given_loss(loss, c)
+    if alpha is not None:
+        loss = loss_model(c, alpha, alpha_power, alpha_band, dt, mechanisms)
+    if loss is not None:
+        if loss["speed"] * dt / h > stability_limit(R):
+            raise DasError(f"fdtd: with absorption the fastest speed is {loss['speed']:.1f} m/s and c dt / h = {loss['speed'] * dt / h:.4f} is above the "
+                           f"stability limit {stability_limit(R):.4f} of order {2 * R}")
     tab = prepare(c, rho, h, dt, P)
     Nz, Nx = tab["Nz"], tab["Nx"]
     s_host = None if isinstance(s, torch.Tensor) else np.asarray(s, np.float64)
@@ -249,6 +398,11 @@ def fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt, PML=20, order=8,
     if ld < Nz:
         raise DasError(f"fdtd: ld = {ld} is less than Nz = {Nz}")
     meta = dict(Nz=Nz, Nx=Nx, Nt=Nt, ld=ld, M=M, Ts=Ts, N=N, dt_h=dt / h, inv_h=1.0 / h, double=prec == "double", order=2 * R)
+    Lm = 0
+    if loss is not None:                                         # the map joins the tables under "kap"; launch() takes it out again
+        tb["kap"] = up(np.ascontiguousarray(np.pad(loss["kap"], P, mode="edge").T))
+        meta["loss"] = {k: loss[k] for k in ("mode", "L", "y", "tau", "E", "g", "fit_err", "speed")}
+        Lm = loss["L"]
     if prepare_only:
         return meta, tb, s_dev
     rec = torch.empty((Nt, N, V), dtype=rdt, device=dev)
@@ -260,17 +414,21 @@ def fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt, PML=20, order=8,
             Vb = min(bs, V - v0)
             if return_state or pool is None:
                 pool = {k: torch.empty((Vb, Nx, ld), dtype=rdt, device=dev) for k in STATES}
-            st = {k: pool[k][:Vb] for k in STATES}
-            for k in STATES:
+                if Lm:
+                    pool["e"] = torch.empty((Vb, Lm, Nx, ld), dtype=rdt, device=dev)
+            st = {k: pool[k][:Vb] for k in pool}
+            for k in st:
                 st[k].zero_()
             launch(meta, tb, st, s_dev[:, :, v0:v0 + Vb].contiguous(), rec, v0)
             if return_state:
-                for k in STATES:
-                    states[k].append(st[k][:, :, :Nz])
+                for k in st:
+                    states.setdefault(k, []).append(st[k][..., :Nz])
     if not return_state:
         return rec
     cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, 0)
     empty = torch.zeros((0, Nx, Nz), dtype=rdt, device=dev)
+    if Lm and not states.get("e"):
+        states["e"] = [torch.zeros((0, Lm, Nx, Nz), dtype=rdt, device=dev)]
     return rec, {k: (cat(v) if v else empty) for k, v in states.items()}
 
 
@@ -280,7 +438,10 @@ STATES = ("p", "uz", "ux", "rz", "rx")
 def launch(meta, tb, st, sb, rec, v0=0, stream=None):
     """one call of ``qdas_fdtd``: ``meta`` the sizes and scalars, ``tb`` the device tables by the names of ``qdas_fdtd_args``, ``st`` the five state tensors
     ``Vb x Nx x ld`` (zero for a start from rest), ``sb`` the source table ``T' x M x Vb`` (contiguous), ``rec`` the whole record ``Nt x N x V`` of which the
-    pulses ``v0 .. v0 + Vb - 1`` are written.  ``stream``: a ``torch.cuda.Stream`` (default: the current one).  Only enqueues."""
+    pulses ``v0 .. v0 + Vb - 1`` are written.  ``stream``: a ``torch.cuda.Stream`` (default: the current one).  Only enqueues.
+
+    With ``meta["loss"]`` (``mode``, ``L``, ``g``, ``E``) the call is ``qdas_fdtd_lossy``: ``tb["kap"]`` is the loss map and ``st["e"]`` the memory
+    variables ``Vb x L x Nx x ld`` (relaxation only)."""
     import torch
     dev = st["p"].device
     Vb = int(st["p"].shape[0])
@@ -299,9 +460,22 @@ def launch(meta, tb, st, sb, rec, v0=0, stream=None):
     for k in STATES:
         setattr(a, k, ptr(st[k]))
     for k, t in tb.items():
-        setattr(a, k, ptr(t))
+        if k != "kap":
+            setattr(a, k, ptr(t))
     a.s = ptr(sb)
     a.rec = C.c_void_p(rec.data_ptr() + v0 * rec.stride(2) * rec.element_size()) if rec.numel() else None
-    _lib.check(_lib.lib().qdas_fdtd(C.byref(d), C.byref(a)))
+    loss = meta.get("loss")
+    if loss is None:
+        _lib.check(_lib.lib().qdas_fdtd(C.byref(d), C.byref(a)))
+    else:
+        q = _lib.FdtdLoss()
+        q.mode, q.L = (_lib.FDTD_LOSS_STOKES if loss["mode"] == "stokes" else _lib.FDTD_LOSS_RELAX), int(loss["L"])
+        for k in range(q.L):
+            q.g[k], q.E[k] = float(loss["g"][k]), float(loss["E"][k])
+        q.kap = ptr(tb.get("kap"))
+        q.e = ptr(st.get("e"))
+        if q.L and st.get("e") is not None and (tuple(st["e"].shape[:2]) != (Vb, q.L) or tuple(st["e"].stride()) != (q.L * d.vstride, d.vstride, d.ld, 1)):
+            raise DasError(f"fdtd: the memory variables are Vb x L x Nx x ld = {Vb} x {q.L} x {meta['Nx']} x {meta['ld']} in the states' layout")
+        _lib.check(_lib.lib().qdas_fdtd_lossy(C.byref(d), C.byref(a), C.byref(q)))
     if sb.numel():
         sb.record_stream(stream)

@@ -533,7 +533,8 @@ class UltrasoundSystem:
         return self.focusTx(chd, self.seq, interp=interp) if focus else chd
 
     def fdtdSim(self, c, rho=None, cgrd: Scan | None = None, *, waveform, wv_t0, wv_fs, rx_impulse=None, rx_t0=0.0, c0=None, rho0=None, T=None, PML=20,
-                CFL_max=0.25, order=8, isosub=False, field=False, bsize=None, prec="single", ElemMapMethod="nearest", plan_only=False):
+                CFL_max=0.25, order=8, isosub=False, field=False, bsize=None, prec="single", ElemMapMethod="nearest", plan_only=False,
+                alpha=None, alpha_power=1.01, alpha_band=None, mechanisms=3):
         """``chd = fdtdSim(us, c, rho, cgrd)``: channel data that travelled through the medium ``c``, ``rho`` (``Z x X`` on the Cartesian scan ``cgrd``, by
         default this system's scan), from a 2-D acoustic FDTD solver on the device (``qups_amd/fdtd.py`` -> ``qdas_fdtd``).  It follows the wrapper contract of
         the reference's ``kspaceFirstOrder`` (``src/UltrasoundSystem.m:2458-3170``) -- the time step from ``CFL_max`` as an integer fraction of ``1 / us.fs``
@@ -548,7 +549,16 @@ class UltrasoundSystem:
         ``fs_ = ratio us.fs``, as the reference returns it: the caller downsamples.  ``field=True``: the pressure of the whole interior grid per step,
         ``T x (Z X) x V`` (sensors = all nodes, ``Z`` slowest, no receive impulse), refused above 2 GiB.  ``plan_only``: the wrapper arithmetic alone, a dict
         (no device needed).  A ``cgrd`` with three non-singleton dimensions goes to the 3-D solver (``qups_amd/fdtd3.py`` -> ``qdas_fdtd3``): ``c``, ``rho`` of
-        ``cgrd.size``, ``field`` as ``T x (Z X Y) x V``.  Not built: absorption, nonlinearity, ``'linear'`` and ``karray-*`` element mapping, sensor directivity."""
+        ``cgrd.size``, ``field`` as ``T x (Z X Y) x V``.
+
+        ABSORPTION (2-D).  ``alpha``: a scalar or a map on ``cgrd`` in dB/(MHz^y cm), k-Wave's ``alpha_coeff`` -- ``1e4 Medium.alpha0``, the conversion of
+        the reference's ``Medium.getMediumKWave`` (``src/Medium.m:443``) -- with ``alpha_power = y`` (``Medium.alpha_power``, default 1.01).  ``1 <= y < 2``:
+        ``mechanisms <= 4`` relaxation mechanisms fitted to ``w^y`` over ``alpha_band`` (default ``(0.5 fc, 1.5 fc)`` of the transducer): a relaxation FDTD
+        of the Fullwave kind, NOT k-Wave's fractional Laplacian; ``y = 2``: k-Wave's ``alpha_mode = 'stokes'``.  The time step respects the unrelaxed speed
+        (``fdtd.loss_time_step``), and ``plan["loss"]["fit_err"]`` is the fit's largest relative deviation from the power law inside the band.
+        ``alpha=None``: lossless, as before.  ``y`` outside ``[1, 2]`` or a negative ``alpha``: ``ValueError``; a volume with ``alpha``:
+        ``NotImplementedError``.  Not built: absorption in 3-D, nonlinearity, a per-node ``alpha_power``, ``'linear'`` and ``karray-*`` element mapping,
+        sensor directivity."""
         from . import fdtd as F
         if ElemMapMethod != "nearest":
             if ElemMapMethod in ("linear", "karray-direct", "karray-depend"):
@@ -560,6 +570,8 @@ class UltrasoundSystem:
         if cgrd.axes is None or cgrd.axes.get("kind") != "cartesian":
             raise DasError("fdtdSim: cgrd must be a Cartesian scan made by Scan.cartesian (order 'ZXY').")
         if sum(int(v) > 1 for v in tuple(cgrd.size)) == 3:           # three non-singleton dimensions -> the 3-D solver (reference :2929-2948), as in bfEikonal
+            if alpha is not None:
+                raise NotImplementedError("fdtdSim: absorption is built for the 2-D solver only; a volume takes alpha=None")
             return self._fdtdSim3(c, rho, cgrd, waveform=waveform, wv_t0=wv_t0, wv_fs=wv_fs, rx_impulse=rx_impulse, rx_t0=rx_t0, c0=c0, rho0=rho0, T=T, PML=PML,
                                   CFL_max=CFL_max, order=order, isosub=isosub, field=field, bsize=bsize, prec=prec, plan_only=plan_only)
         z, x = cgrd.axes["z"], cgrd.axes["x"]
@@ -578,7 +590,13 @@ class UltrasoundSystem:
         rho = rho.reshape(Z, X)
         if self.fs is None:
             raise DasError("fdtdSim: the system needs a sampling frequency fs")
-        ratio, fs_, dt = F.time_step(self.fs, c.max(), h, CFL_max, order)
+        loss = None
+        if alpha is None:
+            ratio, fs_, dt = F.time_step(self.fs, c.max(), h, CFL_max, order)
+        else:
+            if alpha_band is None:
+                alpha_band = (0.5 * float(self.xdc.fc), 1.5 * float(self.xdc.fc))
+            ratio, fs_, dt, loss = F.loss_time_step(self.fs, c, alpha, alpha_power, alpha_band, h, CFL_max, order, mechanisms)
         s, txn0, txne = F.tx_table(waveform, wv_t0, wv_fs, self.seq.delays(self.tx), self.seq.apodization(self.tx), fs_)
         if T is None:
             T = 2.0 * math.hypot(z[-1] - z[0], x[-1] - x[0]) / c0
@@ -587,6 +605,10 @@ class UltrasoundSystem:
         rx_t0 = float(rx_t0) if (rx_impulse is not None and not field) else 0.0
         plan = dict(h=h, ratio=ratio, fs_=fs_, dt=dt, txn0=txn0, txne=txne, Nt=Nt, t0=txn0 / fs_ + rx_t0, P=P, Nz=Z + 2 * P, Nx=X + 2 * P, T=float(T),
                     rho=rho, rho_iso=F.iso_density(c, c0, rho0) if isosub else None)
+        lkw = {}
+        if loss is not None:
+            plan["loss"] = loss
+            lkw = dict(alpha=alpha, alpha_power=alpha_power, alpha_band=alpha_band, mechanisms=mechanisms)
         nrm = np.stack([self.tx.normals[2], self.tx.normals[0]])
         V = s.shape[2]
         if field:
@@ -599,7 +621,7 @@ class UltrasoundSystem:
         plan.update(src_nodes=(siz, six), sen_nodes=F.nearest_nodes(z, x, sen) if not field else None)
         if plan_only:
             return plan
-        run = lambda r: F.fdtd(c, r, z, x, self.tx.positions(), nrm, s, sen, Nt, dt, PML=P, order=order, prec=prec, bsize=bsize, sen_nodes=sen_nodes)
+        run = lambda r: F.fdtd(c, r, z, x, self.tx.positions(), nrm, s, sen, Nt, dt, PML=P, order=order, prec=prec, bsize=bsize, sen_nodes=sen_nodes, **lkw)
         y = run(rho)
         if isosub:
             y = y - run(plan["rho_iso"])
