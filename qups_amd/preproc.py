@@ -101,6 +101,21 @@ def hilbert(x, N: int | None = None, fdown: float = 0.0, t0: float = 0.0, fs: fl
     ``N`` (default ``T``; zero-padded or truncated like MATLAB's ``hilbert(x, N)``); with ``fdown`` the result is also multiplied by
     ``exp(-2j*pi*fdown*(t0 + k/fs))``.  Returns a complex64 torch tensor ``N x ...`` on the device.
 
+    Traces are transformed in pairs.  With the trailing dimensions flattened in row-major order (``k = n * M + m`` for ``T x N x M``), traces ``2j`` and ``2j + 1``
+    ride ONE complex transform ``z = x1 + i x2`` (what makes this one pass over HBM); an odd count leaves the last trace alone, and with an odd channel count pairs
+    straddle transmits.  What follows from that, and is tested (``tests/test_gpu_neighbours.py``):
+
+    * the real part of every trace is its input, bit for bit (without ``fdown``), whatever its partner holds;
+    * ``H x1 = Im(..) - x2`` and ``H x2 = x1 - Re(..)`` cancel against the partner, so the rounding error of a trace is relative to the LARGER of the two: measured at
+      most 5.5e-7 of the pair's ``max|y|`` on an MI355X (each pair scaled as a unit by 2^0, 2^20, 2^-20 or 2^7) -- so a trace 2^10 below its partner carries about 1e-4 of its OWN maximum,
+      one 2^20 below about 0.15 (a float32 restatement of the packing on the CPU gives 9.2e-5 .. 1.6e-4 and 0.14 .. 0.15 at N = 256 and 2816), and an all-zero trace
+      gets its partner's rounding noise as imaginary part.  Scale a quiet trace up first if that matters;
+    * a NaN or Inf sample turns the imaginary part of BOTH traces of its pair non-finite at all ``N`` samples, and changes no bit of any other pair;
+    * scaling a pair by a power of two scales its result exactly.
+
+    Lengths the one-pass kernel does not serve (a prime factor above 13, stages too wide, more than 8192 samples), and every length under
+    ``QDAS_PRE_HIPFFT=1``, go through hipFFT trace by trace: there each trace depends on itself alone.  So whether two neighbours couple depends on ``N``.
+
     ``t0``, ``fs`` and ``fdown`` are constants of the underlying plan (``qdas_pre_desc``), so they are part of the plan cache's key: a frame loop whose ``t0`` changes
     per frame creates a plan per value (0.1 ms on the one-pass path, 11-15 ms where hipFFT plans are made) -- downmix with ``t0 = 0`` and multiply the frame by the
     scalar ``exp(-2j*pi*fdown*t0)`` instead."""

@@ -65,7 +65,8 @@ def test_hilbert_matches_numpy(T, N, dtype, fdown):
                                                (1536, None, 2, "i16", 0.0)])      # 3 8 8 8, 256 threads with two butterflies each
 def test_one_pass_hilbert_matches_numpy(T, N, K, dtype, fdown, force_hipfft, monkeypatch):
     """the LDS-resident kernel (two real traces per complex transform, mixed-radix stages LDS to LDS) against the numpy restatement,
-    and the hipFFT passes it replaces against the same numbers"""
+    and the hipFFT passes it replaces against the same numbers.  (Per PAIR of traces over the pair's own max|ref|, each pair scaled as a unit by 2^0, 2^20, 2^-20 or 2^7: largest 5.5e-7 = 0.028 of
+    this bound on an MI355X -- tests/test_gpu_neighbours.py, which also states what the pairing does to a quiet trace beside a loud one.)"""
     from qups_amd.preproc import hilbert
     monkeypatch.setenv("QDAS_PRE_HIPFFT", "1" if force_hipfft else "0")
     rng = np.random.default_rng(T + K)
