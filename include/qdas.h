@@ -913,6 +913,26 @@ typedef struct qdas_fdtd_loss {
 } qdas_fdtd_loss;
 int qdas_fdtd_lossy(const qdas_fdtd_desc *d, const qdas_fdtd_args *a, const qdas_fdtd_loss *l);
 
+/* ---- qdas_fdtd with nonlinear propagation (B/A), with or without absorption: k-Wave's nonlinear first-order equations on the staggered grid of qdas_fdtd.
+ * Steps 1, 2 and 5 are qdas_fdtd's.  With ro = rz + rx before step 3 and rn = rz + rx after it:
+ *   3'. r_a <- A_a (A_a r_a - (dt / h) (rho + K ro) h D-_a u_a)      a in {z, x};  K = 2 (the convective term), 0 with QDAS_FDTD_NL_NO_CONVECTIVE
+ *   4'. p = c2 (rn + [the absorption term of qdas_fdtd_lossy, if l is given] + bq rn^2)
+ * bq = BoA / (2 rho) is an Nx x Nz dense map like the medium's; a node with bq = 0 takes the linear value itself.  For a progressive plane wave this is
+ * Westervelt's equation with beta = 1 + B/2A (the convective term alone: beta = 1, the quadratic term alone: beta = B/2A).  The source samples are particle
+ * velocities in m/s (a line of additive sources s = v0 radiates rho c v0 each way): their absolute size matters here.  There is no shock capturing: without
+ * absorption a wave that reaches the shock distance (sigma = 1) rings at the grid scale.
+ * l = NULL: no absorption; otherwise the loss block of qdas_fdtd_lossy with all its rules.  With QDAS_FDTD_NL_NO_CONVECTIVE and an all-zero bq the entry
+ * gives the bits of qdas_fdtd (l = NULL) and of qdas_fdtd_lossy (l given).  Still two launches per step (the velocity pass is qdas_fdtd's kernel), no
+ * atomics, two runs give the same bits, pulses never mix.
+ * Validation, on the host before any HIP call: every row of qdas_fdtd and, with l, of qdas_fdtd_lossy; a null nonlinear block, unknown flags in it, and --
+ * for a call that has work -- a null bq: QDAS_EINVAL.  Nt = 0 or V = 0: QDAS_OK, nothing is launched. */
+#define QDAS_FDTD_NL_NO_CONVECTIVE 1
+typedef struct qdas_fdtd_nl {
+    const void *bq;                    /* Nx x Nz: BoA / (2 rho)                                              */
+    int32_t flags;                     /* 0 | QDAS_FDTD_NL_NO_CONVECTIVE                                      */
+} qdas_fdtd_nl;
+int qdas_fdtd_nonlinear(const qdas_fdtd_desc *d, const qdas_fdtd_args *a, const qdas_fdtd_loss *l /* NULL: lossless */, const qdas_fdtd_nl *q);
+
 /* ---- 3-D acoustic FDTD (fdtd3.hip): the scheme of qdas_fdtd with a third axis -- linear, lossless, first order in time, of order 2R in space (R = 1, 2, 4)
  * on a staggered grid -- for channel data through volumes (the reference's kspaceFirstOrder picks kspaceFirstOrder3D for a grid of three dimensions,
  * src/UltrasoundSystem.m:2929-2948).  FDTD, NOT k-space pseudospectral.

@@ -83,6 +83,8 @@
  *         2-D acoustic FDTD from rest, the record of the sensors; described at cmd_fdtd below.
  *   rec     = qdas_mex('fdtdloss', med, pml, s, src, sen, [Nz Nx V Nt dt_h inv_h order], kap, [mode g E])
  *         the same with power-law absorption (qdas_fdtd_lossy); described at cmd_fdtd below.
+ *   rec     = qdas_mex('fdtdnl', med, pml, s, src, sen, [Nz Nx V Nt dt_h inv_h order], bq, flags[, kap, [mode g E]])
+ *         the same with nonlinear propagation, with or without absorption (qdas_fdtd_nonlinear); described at cmd_fdtd below.
  *   rec     = qdas_mex('fdtd3', med, pml, s, src, sen, [Nz Nx Ny V Nt dt_h inv_h order])
  *         the same through a volume; described at cmd_fdtd3 below.
  * Host arrays are staged through device memory by the gateway (qdas_device_malloc / _copy / _free: no HIP headers needed); with -DQDAS_MEX_GPU gpuArrays
@@ -1250,10 +1252,15 @@ static mxArray *cmd_resample(int nrhs, const mxArray *prhs[]) {
  * allowed: the record is then all zeros.
  * rec = qdas_mex('fdtdloss', med, pml, s, src, sen, prm, kap, loss) -- the same with absorption (qdas_fdtd_lossy).  kap: Nz x Nx of the class of med, the loss
  * map extended like the medium (2 c a under relaxation, 2 c a / dt under Stokes; qups_amd/fdtd.py `loss_model` is the recipe).  loss: host values
- * [mode g(1 .. L) E(1 .. L)], mode 1 = Stokes (L = 0) | 2 = relaxation (L = 1 .. 4).  The L memory variables per pulse are scratch of the call like the states. */
-static mxArray *cmd_fdtd(int nrhs, const mxArray *prhs[], int lossy) {
-    if (nrhs != (lossy ? 8 : 6))
-        mexErrMsgIdAndTxt("QUPS:das_spec:nargin", lossy ? "qdas_mex('fdtdloss', med, pml, s, src, sen, prm, kap, loss)" : "qdas_mex('fdtd', med, pml, s, src, sen, prm)");
+ * [mode g(1 .. L) E(1 .. L)], mode 1 = Stokes (L = 0) | 2 = relaxation (L = 1 .. 4).  The L memory variables per pulse are scratch of the call like the states.
+ * rec = qdas_mex('fdtdnl', med, pml, s, src, sen, prm, bq, flags[, kap, loss]) -- the same with nonlinear propagation (qdas_fdtd_nonlinear).  bq: Nz x Nx of
+ * the class of med, B/A / (2 rho) extended like the medium (qups_amd/fdtd.py `nl_model` is the recipe); flags: one host value, 0 | 1 (no convective term);
+ * kap and loss as for 'fdtdloss', both or neither.  The source table is in m/s. */
+static mxArray *cmd_fdtd(int nrhs, const mxArray *prhs[], int kind) {                                   /* kind 0: 'fdtd', 1: 'fdtdloss', 2: 'fdtdnl' */
+    const int nonlin = kind == 2, lossy = kind == 1 || (nonlin && nrhs == 10), ki = nonlin ? 8 : 6;     /* ki: where kap sits; loss follows it */
+    if (nonlin ? (nrhs != 8 && nrhs != 10) : nrhs != (lossy ? 8 : 6))
+        mexErrMsgIdAndTxt("QUPS:das_spec:nargin", nonlin ? "qdas_mex('fdtdnl', med, pml, s, src, sen, prm, bq, flags[, kap, loss])" :
+                          lossy ? "qdas_mex('fdtdloss', med, pml, s, src, sen, prm, kap, loss)" : "qdas_mex('fdtd', med, pml, s, src, sen, prm)");
     const mxClassID cls = mxGetClassID(prhs[0]);
     if ((cls != mxDOUBLE_CLASS && cls != mxSINGLE_CLASS) || mxIsComplex(prhs[0])) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtd: med must be real single or double.");
     if (mxGetClassID(prhs[1]) != cls || mxGetClassID(prhs[2]) != cls || mxIsComplex(prhs[1]) || mxIsComplex(prhs[2]))
@@ -1283,20 +1290,29 @@ static mxArray *cmd_fdtd(int nrhs, const mxArray *prhs[], int lossy) {
     qdas_fdtd_loss q;
     memset(&q, 0, sizeof q);
     if (lossy) {
-        if (mxGetClassID(prhs[6]) != cls || mxIsComplex(prhs[6]) || mxGetNumberOfElements(prhs[6]) != cells)
+        if (mxGetClassID(prhs[ki]) != cls || mxIsComplex(prhs[ki]) || mxGetNumberOfElements(prhs[ki]) != cells)
             mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtdloss: kap must be Nz x Nx, real and of the class of med.");
-        const size_t nl = mxGetNumberOfElements(prhs[7]);
+        const size_t nl = mxGetNumberOfElements(prhs[ki + 1]);
         if (nl < 1 || nl % 2 != 1 || nl > 1 + 2 * QDAS_FDTD_MAX_L) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtdloss: loss = [mode g(1 .. L) E(1 .. L)] with L <= 4.");
-        const double mn = num_at(prhs[7], 0, "loss");
+        const double mn = num_at(prhs[ki + 1], 0, "loss");
         q.mode = (mn == floor(mn) && fabs(mn) < 1e6) ? (int32_t)mn : -1;
         q.L = (int32_t)(nl / 2);
-        for (int k = 0; k < q.L; ++k) { q.g[k] = num_at(prhs[7], (mwSize)(1 + k), "loss"); q.E[k] = num_at(prhs[7], (mwSize)(1 + q.L + k), "loss"); }
+        for (int k = 0; k < q.L; ++k) { q.g[k] = num_at(prhs[ki + 1], (mwSize)(1 + k), "loss"); q.E[k] = num_at(prhs[ki + 1], (mwSize)(1 + q.L + k), "loss"); }
+    }
+    qdas_fdtd_nl w;
+    memset(&w, 0, sizeof w);
+    if (nonlin) {
+        if (mxGetClassID(prhs[6]) != cls || mxIsComplex(prhs[6]) || mxGetNumberOfElements(prhs[6]) != cells)
+            mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtdnl: bq must be Nz x Nx, real and of the class of med.");
+        if (mxGetNumberOfElements(prhs[7]) != 1) mexErrMsgIdAndTxt("QUPS:das_spec:qdas", "fdtdnl: flags is one value, 0 or 1 (no convective term).");
+        const double fn = num_at(prhs[7], 0, "flags");
+        w.flags = (fn == floor(fn) && fabs(fn) < 1e6) ? (int32_t)fn : -1;
     }
     const mwSize dims[3] = {(mwSize)d.Nt, (mwSize)d.N, (mwSize)d.V};
     if (d.Nt * d.V == 0 || d.N == 0) {
         const uint64_t keep = d.Nt;
         if (d.N == 0) d.Nt = 0;                                                                       /* no sensors: nothing to run, but the call is still validated */
-        const int rc = lossy ? qdas_fdtd_lossy(&d, NULL, &q) : (d.N == 0 ? QDAS_OK : qdas_fdtd(&d, NULL));
+        const int rc = nonlin ? qdas_fdtd_nonlinear(&d, NULL, lossy ? &q : NULL, &w) : lossy ? qdas_fdtd_lossy(&d, NULL, &q) : (d.N == 0 ? QDAS_OK : qdas_fdtd(&d, NULL));
         d.Nt = keep;
         if (rc) CFAIL("%s", qdas_last_error());
         release_devargs();
@@ -1349,11 +1365,12 @@ static mxArray *cmd_fdtd(int nrhs, const mxArray *prhs[], int lossy) {
     const size_t bytes = (size_t)(d.Nt * d.N * d.V) * rs;
     mxArray *host;
     if (lossy) {
-        q.kap = dev_in(prhs[6], cells * rs, "kap", &dev);
+        q.kap = dev_in(prhs[ki], cells * rs, "kap", &dev);
         q.e = q.L ? ds + 5 * sb : NULL;
     }
+    if (nonlin) w.bq = dev_in(prhs[6], cells * rs, "bq", &dev);
     a.rec = dev_out(3, dims, cls, 0, dev, bytes, &host);
-    return finish(lossy ? qdas_fdtd_lossy(&d, &a, &q) : qdas_fdtd(&d, &a), host, bytes);
+    return finish(nonlin ? qdas_fdtd_nonlinear(&d, &a, lossy ? &q : NULL, &w) : lossy ? qdas_fdtd_lossy(&d, &a, &q) : qdas_fdtd(&d, &a), host, bytes);
 }
 
 /* rec = qdas_mex('fdtd3', med, pml, s, src, sen, prm) -- Nt steps of the 3-D acoustic FDTD scheme (qdas_fdtd3, include/qdas.h) from rest, on tables the caller
@@ -1506,6 +1523,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         } else if (!strcmp(cmd, "resample")) { plhs[0] = cmd_resample(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "fdtd")) { plhs[0] = cmd_fdtd(nrhs - 1, prhs + 1, 0);
         } else if (!strcmp(cmd, "fdtdloss")) { plhs[0] = cmd_fdtd(nrhs - 1, prhs + 1, 1);
+        } else if (!strcmp(cmd, "fdtdnl")) { plhs[0] = cmd_fdtd(nrhs - 1, prhs + 1, 2);
         } else if (!strcmp(cmd, "fdtd3")) { plhs[0] = cmd_fdtd3(nrhs - 1, prhs + 1);
         } else if (!strcmp(cmd, "destroy")) {
             if (nrhs >= 2) destroy_slot(slot_of(prhs[1])); else destroy_all();

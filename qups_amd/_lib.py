@@ -42,7 +42,7 @@ SYMBOLS = (
     "qdas_raypaths_slots", "qdas_raypaths_weights", "qdas_raypaths_integrate", "qdas_raypaths_backproject",
     "qdas_eikonal3", "qdas_eikonal3_tables", "qdas_eikonal3_work_bytes", "qdas_eikonal3_pass_cap",
     "qdas_scanconvert", "qdas_demod", "qdas_demod_len", "qdas_resample", "qdas_resample_len", "qdas_upfirdn_len",
-    "qdas_fdtd", "qdas_fdtd_tiles", "qdas_fdtd_tile_lists", "qdas_fdtd_lossy",
+    "qdas_fdtd", "qdas_fdtd_tiles", "qdas_fdtd_tile_lists", "qdas_fdtd_lossy", "qdas_fdtd_nonlinear",
     "qdas_fdtd3", "qdas_fdtd3_bricks", "qdas_fdtd3_brick_lists",
 )
 
@@ -222,6 +222,13 @@ class FdtdLoss(C.Structure):
     _fields_ = [("mode", C.c_int32), ("L", C.c_int32), ("g", C.c_double * 4), ("E", C.c_double * 4), ("kap", C.c_void_p), ("e", C.c_void_p)]
 
 
+FDTD_NL_NO_CONVECTIVE = 1
+
+
+class FdtdNl(C.Structure):
+    _fields_ = [("bq", C.c_void_p), ("flags", C.c_int32)]
+
+
 FDTD3_TZ, FDTD3_TX, FDTD3_TY, FDTD3_ZERO = 64, 8, 8, 1
 
 
@@ -332,6 +339,7 @@ def lib():
     L.qdas_upfirdn_len.restype = C.c_uint64
     L.qdas_fdtd.argtypes = [C.POINTER(FdtdDesc), C.POINTER(FdtdArgs)]
     L.qdas_fdtd_lossy.argtypes = [C.POINTER(FdtdDesc), C.POINTER(FdtdArgs), C.POINTER(FdtdLoss)]
+    L.qdas_fdtd_nonlinear.argtypes = [C.POINTER(FdtdDesc), C.POINTER(FdtdArgs), C.POINTER(FdtdLoss), C.POINTER(FdtdNl)]
     L.qdas_fdtd_tiles.argtypes = [C.c_uint64, C.c_uint64]
     L.qdas_fdtd_tiles.restype = C.c_uint64
     L.qdas_fdtd_tile_lists.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]

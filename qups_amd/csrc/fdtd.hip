@@ -78,6 +78,25 @@ __global__ void __launch_bounds__(LANES) density_lossy_kernel(const Params<T> P,
     }
 }
 
+// the nonlinear density pass (qdas_fdtd_nonlinear): density_kernel with density_cells_nl.  L = 0 serves no absorption (Q.kap null) and Stokes alike -- ro is
+// needed by the convective term anyway -- and L = 1 .. 4 relaxation.  The map bq adds one word of traffic per node.
+template <int R, typename T, int L>
+__global__ void __launch_bounds__(LANES) density_nl_kernel(const Params<T> P, const int64_t n, const Loss<T> Q, const Nl<T> N) {
+    __shared__ T lds[lds_words_den(R)];
+    T *lz = lds, *lx = lds + (TZ + 2 * R) * TX;
+    const int t = threadIdx.x, tile = blockIdx.x, v = blockIdx.y;
+    const int i0 = (tile % P.ntz) * TZ, j0 = (tile / P.ntz) * TX;
+    const int64_t off = (int64_t)v * P.vs;
+    stage(lz, P.uz + off, i0, j0, R, 0, P.Nz, P.Nx, P.ld, t);
+    stage(lx, P.ux + off, i0, j0, 0, R, P.Nz, P.Nx, P.ld, t);
+    __syncthreads();
+    density_cells_nl<R, T, L>(P, Q, N, lz, lx, P.rz + off, P.rx + off, P.p + off, L > 0 ? Q.e + off * L : nullptr, i0, j0, t);
+    if (P.N > 0 && P.sen_start[tile + 1] > P.sen_start[tile]) {      // (uniform)
+        __syncthreads();
+        record(P, P.p + off, tile, n, v, t);
+    }
+}
+
 // the host loop of every variant: `den` is the density kernel of the call, `x` what it takes after (P, n)
 template <int R, typename T, typename Den, typename... X>
 static void run(const Params<T> &P, hipStream_t s, uint64_t Nt, uint64_t Ts, Den den, X... x) {
@@ -130,16 +149,49 @@ static void run_mechanisms(const Params<T> &P, const Loss<T> &Q, int L, hipStrea
 }
 
 template <typename T>
-static void run_order_lossy(const qdas_fdtd_desc *d, const qdas_fdtd_args *a, const qdas_fdtd_loss *l, hipStream_t s) {
-    const Params<T> P = params<T>(d, a);
+static Loss<T> loss_block(const qdas_fdtd_loss *l) {
     Loss<T> Q;
     memset(&Q, 0, sizeof Q);
+    if (!l) return Q;
     Q.kap = (const T *)l->kap; Q.e = (T *)l->e;
     for (int k = 0; k < l->L; ++k) { Q.g[k] = (T)l->g[k]; Q.E[k] = (T)l->E[k]; }
+    return Q;
+}
+
+template <typename T>
+static void run_order_lossy(const qdas_fdtd_desc *d, const qdas_fdtd_args *a, const qdas_fdtd_loss *l, hipStream_t s) {
+    const Params<T> P = params<T>(d, a);
+    const Loss<T> Q = loss_block<T>(l);
     switch (d->order) {
         case 2:  run_mechanisms<1, T>(P, Q, l->L, s, d->Nt, d->Ts); break;
         case 4:  run_mechanisms<2, T>(P, Q, l->L, s, d->Nt, d->Ts); break;
         default: run_mechanisms<4, T>(P, Q, l->L, s, d->Nt, d->Ts); break;
+    }
+}
+
+template <int R, typename T>
+static void run_mechanisms_nl(const Params<T> &P, const Loss<T> &Q, const Nl<T> &N, int L, hipStream_t s, uint64_t Nt, uint64_t Ts) {
+    switch (L) {
+        case 0:  run<R, T>(P, s, Nt, Ts, density_nl_kernel<R, T, 0>, Q, N); break;
+        case 1:  run<R, T>(P, s, Nt, Ts, density_nl_kernel<R, T, 1>, Q, N); break;
+        case 2:  run<R, T>(P, s, Nt, Ts, density_nl_kernel<R, T, 2>, Q, N); break;
+        case 3:  run<R, T>(P, s, Nt, Ts, density_nl_kernel<R, T, 3>, Q, N); break;
+        default: run<R, T>(P, s, Nt, Ts, density_nl_kernel<R, T, 4>, Q, N); break;
+    }
+}
+
+template <typename T>
+static void run_order_nl(const qdas_fdtd_desc *d, const qdas_fdtd_args *a, const qdas_fdtd_loss *l, const qdas_fdtd_nl *q, hipStream_t s) {
+    const Params<T> P = params<T>(d, a);
+    const Loss<T> Q = loss_block<T>(l);
+    Nl<T> N;
+    N.bq = (const T *)q->bq;
+    N.K = (q->flags & QDAS_FDTD_NL_NO_CONVECTIVE) ? T(0) : T(2);
+    const int L = l ? l->L : 0;
+    switch (d->order) {
+        case 2:  run_mechanisms_nl<1, T>(P, Q, N, L, s, d->Nt, d->Ts); break;
+        case 4:  run_mechanisms_nl<2, T>(P, Q, N, L, s, d->Nt, d->Ts); break;
+        default: run_mechanisms_nl<4, T>(P, Q, N, L, s, d->Nt, d->Ts); break;
     }
 }
 
@@ -232,10 +284,8 @@ extern "C" int qdas_fdtd(const qdas_fdtd_desc *d, const qdas_fdtd_args *a) {
     return QDAS_OK;
 }
 
-extern "C" int qdas_fdtd_lossy(const qdas_fdtd_desc *d, const qdas_fdtd_args *a, const qdas_fdtd_loss *l) {
-    bool work;
-    int rc = check_desc(d, &work);
-    if (rc != QDAS_OK) return rc;
+// the loss block's rows, before the pointers are looked at
+static int check_loss(const qdas_fdtd_loss *l) {
     if (!l) return fail(QDAS_EINVAL, "fdtd: null loss block");
     if (l->mode != QDAS_FDTD_LOSS_STOKES && l->mode != QDAS_FDTD_LOSS_RELAX) return fail(QDAS_EINVAL, "fdtd: unknown loss mode %d", l->mode);
     if (l->L < 0 || l->L > QDAS_FDTD_MAX_L) return fail(QDAS_EINVAL, "fdtd: L = %d mechanisms, at most %d", l->L, QDAS_FDTD_MAX_L);
@@ -245,21 +295,63 @@ extern "C" int qdas_fdtd_lossy(const qdas_fdtd_desc *d, const qdas_fdtd_args *a,
         if (!isfinite(l->g[k]) || l->g[k] < 0.0) return fail(QDAS_EINVAL, "fdtd: g[%d] = %g must be finite and not negative", k, l->g[k]);
         if (!(l->E[k] > 0.0 && l->E[k] <= 1.0)) return fail(QDAS_EINVAL, "fdtd: E[%d] = %g lies outside (0, 1]", k, l->E[k]);
     }
-    if (!work) return QDAS_OK;
-    if ((rc = check_args(d, a)) != QDAS_OK) return rc;
+    return QDAS_OK;
+}
+
+// the loss block's pointers, for a call that has work
+static int check_loss_work(const qdas_fdtd_desc *d, const qdas_fdtd_loss *l) {
     if (!l->kap || (l->L > 0 && !l->e)) return fail(QDAS_EINVAL, "fdtd: null pointer (the loss map or the memory variables)");
     if (d->V * (uint64_t)(l->L > 0 ? l->L : 1) * d->vstride >= (1ull << 62)) return fail(QDAS_EUNSUPPORTED, "fdtd: the memory variables pass 2^62 elements");
+    return QDAS_OK;
+}
+
+// QDAS_FDTD_ZERO with an optional loss block: the memory variables are V L arrays of the states' layout
+static int clear_all(const qdas_fdtd_desc *d, const qdas_fdtd_args *a, const qdas_fdtd_loss *l, hipStream_t s) {
+    void *st[6] = {a->p, a->uz, a->ux, a->rz, a->rx, l ? l->e : nullptr};
+    int rc;
+    if ((rc = clear_states(d, st, 5, d->V, s)) != QDAS_OK) return rc;
+    if (l && l->L > 0 && (rc = clear_states(d, st + 5, 1, d->V * (uint64_t)l->L, s)) != QDAS_OK) return rc;
+    return QDAS_OK;
+}
+
+extern "C" int qdas_fdtd_lossy(const qdas_fdtd_desc *d, const qdas_fdtd_args *a, const qdas_fdtd_loss *l) {
+    bool work;
+    int rc = check_desc(d, &work);
+    if (rc != QDAS_OK) return rc;
+    if ((rc = check_loss(l)) != QDAS_OK) return rc;
+    if (!work) return QDAS_OK;
+    if ((rc = check_args(d, a)) != QDAS_OK) return rc;
+    if ((rc = check_loss_work(d, l)) != QDAS_OK) return rc;
 
     qdas::DeviceGuard guard(d->device);
     if (guard.err != hipSuccess) return fail(QDAS_EHIP, "hipSetDevice failed: %s", hipGetErrorString(guard.err));
     const hipStream_t s = (hipStream_t)d->queue;
-    if (d->flags & QDAS_FDTD_ZERO) {                    // the memory variables are V L arrays of the states' layout
-        void *st[6] = {a->p, a->uz, a->ux, a->rz, a->rx, l->e};
-        if ((rc = clear_states(d, st, 5, d->V, s)) != QDAS_OK) return rc;
-        if (l->L > 0 && (rc = clear_states(d, st + 5, 1, d->V * (uint64_t)l->L, s)) != QDAS_OK) return rc;
-    }
+    if ((d->flags & QDAS_FDTD_ZERO) && (rc = clear_all(d, a, l, s)) != QDAS_OK) return rc;
     if (d->dtype == QDAS_F32) qdas::fd::run_order_lossy<float>(d, a, l, s);
     else qdas::fd::run_order_lossy<double>(d, a, l, s);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(QDAS_EHIP, "%s", hipGetErrorString(e));
+    return QDAS_OK;
+}
+
+extern "C" int qdas_fdtd_nonlinear(const qdas_fdtd_desc *d, const qdas_fdtd_args *a, const qdas_fdtd_loss *l, const qdas_fdtd_nl *q) {
+    bool work;
+    int rc = check_desc(d, &work);
+    if (rc != QDAS_OK) return rc;
+    if (l && (rc = check_loss(l)) != QDAS_OK) return rc;
+    if (!q) return fail(QDAS_EINVAL, "fdtd: null nonlinear block");
+    if (q->flags & ~QDAS_FDTD_NL_NO_CONVECTIVE) return fail(QDAS_EINVAL, "fdtd: unknown flags 0x%x (the nonlinear block)", (unsigned)q->flags);
+    if (!work) return QDAS_OK;
+    if ((rc = check_args(d, a)) != QDAS_OK) return rc;
+    if (l && (rc = check_loss_work(d, l)) != QDAS_OK) return rc;
+    if (!q->bq) return fail(QDAS_EINVAL, "fdtd: null pointer (the nonlinearity map)");
+
+    qdas::DeviceGuard guard(d->device);
+    if (guard.err != hipSuccess) return fail(QDAS_EHIP, "hipSetDevice failed: %s", hipGetErrorString(guard.err));
+    const hipStream_t s = (hipStream_t)d->queue;
+    if ((d->flags & QDAS_FDTD_ZERO) && (rc = clear_all(d, a, l, s)) != QDAS_OK) return rc;
+    if (d->dtype == QDAS_F32) qdas::fd::run_order_nl<float>(d, a, l, q, s);
+    else qdas::fd::run_order_nl<double>(d, a, l, q, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(QDAS_EHIP, "%s", hipGetErrorString(e));
     return QDAS_OK;

@@ -12,7 +12,8 @@
 //   4. p = c2 (rz + rx)
 //   5. rec[n, j, v] = p[sensor j]
 // Steps 1-2 are the velocity pass, 3-5 the density pass.  With absorption (qdas_fdtd_lossy) step 4 is density_cells_lossy's; every other step is the same
-// text (tests/fdtd_loss_core_host.cpp walks it).
+// text (tests/fdtd_loss_core_host.cpp walks it).  With nonlinear propagation (qdas_fdtd_nonlinear) steps 3 and 4 are density_cells_nl's
+// (tests/fdtd_nl_core_host.cpp).
 //
 // THE TILE.  A workgroup of LANES = 256 lanes owns TZ x TX = 64 x 16 nodes of one pulse: lane t has z offset t mod 64 (a wave is one contiguous row of 64) and
 // the rows (t div 64) + 4 r, r = 0 .. 3.  The velocity pass stages p with a halo of R on every side ((TZ + 2R) x (TX + 2R) words); the density pass stages uz
@@ -181,8 +182,15 @@ struct Loss {
 // and a second kernel with more arithmetic behind the same text is free to fuse differently (it did).  With a zero loss map the lossy pass must give the BITS
 // of the lossless one (tests/test_gpu_fdtd_loss.py), so it states these roundings with explicit fused operations and QDAS_FD_ROUNDED, and the compiler has
 // no choice left.  On the host the same text gives the same values.
+// (a host build with QDAS_FD_UNFUSED and without contraction rounds every product: the arithmetic of the numpy restatements, operation for operation;
+// tests/fdtd_nl_core_host.cpp compares bits with it)
+#if defined(QDAS_FD_UNFUSED) && !defined(__HIPCC__)
+QDAS_FD_HD float fused(float a, float b, float c) { return a * b + c; }
+QDAS_FD_HD double fused(double a, double b, double c) { return a * b + c; }
+#else
 QDAS_FD_HD float fused(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 QDAS_FD_HD double fused(double a, double b, double c) { return __builtin_fma(a, b, c); }
+#endif
 
 template <int R, typename T>
 QDAS_FD_HD T dminus_fused(const T *g, int st) {
@@ -235,6 +243,89 @@ QDAS_FD_UNROLL
         }
         const T k = Q.kap[m];
         p[o] = P.c2[m] * (k != T(0) ? rn + k * acc : rn);      // a node without loss is step 4 itself, the sign of a zero included
+    }
+}
+
+// the nonlinear block of qdas_fdtd_nonlinear: `bq` = BoA / (2 rho) is Nx x Nz dense like the medium maps, K the weight of the convective term (2, or 0 when
+// it is switched off)
+template <typename T>
+struct Nl {
+    const T *bq;
+    T K;
+};
+
+// steps 3' and 4' (nonlinear propagation, with or without absorption) for the nodes of lane t.  ro = rz + rx before the update, rn after it:
+//   3'. r_a <- A_a (A_a r_a - (dt / h) (rho + K ro) h D-_a u_a)
+//   4'. p = c2 (rn + [the absorption term of density_cells_lossy] + bq rn^2)
+// Q.kap == nullptr: no absorption (L = 0).  THE ROUNDINGS are density_cells_lossy's, stated again, so that K = 0 with a zero bq map gives the bits of
+// density_cells (no loss block) and of density_cells_lossy (with one):
+//   * rho + K ro is ONE rounding, fused(K, ro, rho): rho itself for K = 0 (rho + 0 ro);
+//   * the absorption term is written with the fused operations the contracting compiler chose for density_cells_lossy (read from its code objects):
+//     e_l + E_l (rn - e_l) = fused(E_l, rn - e_l, e_l); the sum over l from acc = 0 is fused(g_l, rn - e_l, acc) in double and for l = 0, but in float the
+//     products g_l (rn - e_l), l >= 1, are rounded on their own (that compiler packs them in pairs); rn + kap acc = fused(kap, acc, rn);
+//   * rn^2 is a product of its own, then fused(bq, rn^2, .); a node with bq = 0 takes the linear value itself, as a node with kap = 0 takes rn.
+template <int R, typename T, int L>
+QDAS_FD_HD void density_cells_nl(const Params<T> &P, const Loss<T> &Q, const Nl<T> &N, const T *lz, const T *lx, T *rz, T *rx, T *p, T *e, int i0, int j0,
+                                 int t) {
+    constexpr int W = TZ + 2 * R;
+    const int tz = t % TZ, i = i0 + tz;
+    if (i >= P.Nz) return;
+    const T a = P.az[i];
+QDAS_FD_UNROLL
+    for (int r = 0; r < PER_LANE; ++r) {
+        const int jl = t / TZ + r * ROWS, j = j0 + jl;
+        if (j >= P.Nx) break;
+        const int64_t o = (int64_t)j * P.ld + i, m = (int64_t)j * P.Nz + i;
+        const T oz = rz[o], ox = rx[o];
+        T ro = oz + ox;
+        QDAS_FD_ROUNDED(ro);
+        T re = fused(N.K, ro, P.rho[m]);
+        QDAS_FD_ROUNDED(re);
+        const T b = P.ax[j], w = P.dt_h * re;
+        T wdz = w * dminus_fused<R, T>(lz + jl * W + (tz + R), 1), wdx = w * dminus_fused<R, T>(lx + (jl + R) * TZ + tz, TZ);
+        QDAS_FD_ROUNDED(wdz);
+        QDAS_FD_ROUNDED(wdx);
+        const T iz = fused(a, oz, -wdz), ix = fused(b, ox, -wdx);
+        T vz = a * iz, vx = b * ix;
+        QDAS_FD_ROUNDED(vz);
+        QDAS_FD_ROUNDED(vx);
+        rz[o] = vz;
+        rx[o] = vx;
+        T rn = sizeof(T) == 4 ? vz + vx : fused(a, iz, vx);
+        QDAS_FD_ROUNDED(rn);
+        T lin = rn;
+        if (L > 0 || Q.kap != nullptr) {                          // (uniform)
+            T acc;
+            if (L == 0) {
+                acc = rn - ro;
+            } else {
+                acc = T(0);
+QDAS_FD_UNROLL
+                for (int l = 0; l < L; ++l) {
+                    T *el = e + (int64_t)l * P.vs + o;
+                    const T eo = *el;
+                    T en = fused(Q.E[l], rn - eo, eo);
+                    QDAS_FD_ROUNDED(en);
+                    *el = en;
+                    T gd = rn - en;
+                    QDAS_FD_ROUNDED(gd);
+                    if (sizeof(T) == 4 && l > 0) {
+                        T pr = Q.g[l] * gd;
+                        QDAS_FD_ROUNDED(pr);
+                        acc += pr;
+                    } else {
+                        acc = fused(Q.g[l], gd, acc);
+                    }
+                    QDAS_FD_ROUNDED(acc);
+                }
+            }
+            const T k = Q.kap[m];
+            if (k != T(0)) lin = fused(k, acc, rn);
+        }
+        const T q = N.bq[m];
+        T r2 = rn * rn;
+        QDAS_FD_ROUNDED(r2);
+        p[o] = P.c2[m] * (q != T(0) ? fused(q, r2, lin) : lin);
     }
 }
 

@@ -9,6 +9,10 @@ Absorption is optional (``alpha``, ``alpha_power``): relaxation mechanisms fitte
 term at ``alpha_power = 2`` -- a relaxation FDTD of the Fullwave kind, NOT k-Wave's fractional Laplacian (``qdas_fdtd_lossy``;
 ``tests/fdtd_loss_ref.py`` is its restatement).  Without ``alpha`` the solver is lossless and takes the path it always took.
 
+Nonlinear propagation is optional too (``BoA``): k-Wave's nonlinear first-order equations -- the convective term in the density update and the quadratic
+``B/2A`` term in the equation of state (``qdas_fdtd_nonlinear``; ``tests/fdtd_nl_ref.py`` is its restatement).  Without ``BoA`` the solver is linear and takes
+the paths it always took.
+
 Everything the kernel reads is prepared here on the host in float64 (the extended medium, staggered densities, PML factors, the sampled source table, the
 per-tile point lists) and uploaded once; the states, the record and every table are torch tensors, so the C entry allocates nothing.  There is no CPU
 fallback: without the library or a device the call raises."""
@@ -23,7 +27,7 @@ from . import _lib
 from .das_spec import DasError
 
 __all__ = ["fdtd", "launch", "prepare", "time_step", "stability_limit", "tx_table", "pml_size", "pml_factors", "nearest_nodes", "iso_density", "grid_spacing",
-           "tile_lists", "COEFS", "TILE", "STATES", "relaxation_fit", "relaxation_response", "alpha_np", "loss_model", "loss_time_step", "FIT_SPREADS"]
+           "tile_lists", "COEFS", "TILE", "STATES", "relaxation_fit", "relaxation_response", "alpha_np", "loss_model", "loss_time_step", "FIT_SPREADS", "nl_model", "source_mach"]
 
 COEFS = {1: (1.0,), 2: (9.0 / 8.0, -1.0 / 24.0), 4: (1225.0 / 1024.0, -245.0 / 3072.0, 49.0 / 5120.0, -5.0 / 7168.0)}
 TILE = (_lib.FDTD_TZ, _lib.FDTD_TX)
@@ -292,6 +296,33 @@ def loss_time_step(fs, c, alpha, alpha_power, alpha_band, h, CFL_max=0.25, order
     return ratio, fs_, dt, loss_model(c, alpha, alpha_power, alpha_band, dt, mechanisms)
 
 
+def nl_model(rho, BoA, convective=True):
+    """the nonlinear block of one run from the interior maps, float64: ``None`` for ``BoA = None`` or an all-NaN ``BoA`` (the reference drops ``BonA`` only when
+    every value is NaN, ``src/Medium.m:442-447``: the linear solver), else a dict with ``bq = BoA / (2 rho)`` (``Z x X``), ``convective`` and ``beta_max``:
+    the largest coefficient of nonlinearity ``1 + B/2A`` (``B/2A`` alone without the convective term).  ``BoA = 0`` is still nonlinear (``beta = 1``), as in
+    k-Wave.  ``BoA``: a scalar or a ``Z x X`` map; a map that is partly NaN, or a negative or infinite value, raises ``ValueError``."""
+    if BoA is None:
+        return None
+    rho = np.asarray(rho, np.float64)
+    b = np.asarray(BoA.detach().cpu().numpy() if hasattr(BoA, "detach") else BoA, np.float64)
+    if b.ndim and b.size != rho.size:
+        raise DasError(f"fdtd: BoA is a scalar or a map of the grid's size {rho.shape}, got {b.shape}")
+    if np.isnan(b).all():
+        return None
+    if not np.isfinite(b).all() or (b < 0).any():
+        raise ValueError("fdtd: BoA must be finite and not negative (or NaN everywhere: the linear solver)")
+    b = np.broadcast_to(b.reshape(rho.shape) if b.ndim else b, rho.shape)
+    return dict(bq=b / (2.0 * rho), convective=bool(convective), beta_max=float((1.0 if convective else 0.0) + b.max() / 2.0))
+
+
+def source_mach(s, c, dt, h):
+    """the source Mach number of a transmit table in m/s: ``max|s| (2 c_max dt / h) / c_min`` -- the largest velocity one source node adds in a step (its
+    weight is ``2 c dt / h``) over the slowest speed; a line of sources radiates ``v0 = s`` each way, so this bounds ``u / c`` at the aperture"""
+    c = np.asarray(c, np.float64)
+    s = np.asarray(s, np.float64)
+    return float(np.abs(s).max() * 2.0 * c.max() * float(dt) / float(h) / c.min()) if s.size else 0.0
+
+
 def prepare(c, rho, h, dt, P):
     """the kernel's host tables in float64 from the interior medium ``c``, ``rho`` (``Z x X``): a dict with ``Nz, Nx, c2, rho, dtrz, dtrx`` (``Nx x Nz``, z
     fastest: extended by edge replication, the staggered density the mean of the two neighbours with the last row kept) and ``az, azs, ax, axs``"""
@@ -313,7 +344,7 @@ def prepare(c, rho, h, dt, P):
 
 
 def fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt, PML=20, order=8, prec="single", bsize=None, device=None, return_state=False, ld=None, prepare_only=False,
-         sen_nodes=None, alpha=None, alpha_power=None, alpha_band=None, mechanisms=3, loss=None):
+         sen_nodes=None, alpha=None, alpha_power=None, alpha_band=None, mechanisms=3, loss=None, BoA=None, convective=True):
     """``rec = fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt)``: ``Nt`` steps of the scheme on the grid ``z`` x ``x`` (``c``, ``rho``: ``Z x X``)
     with ``PML`` cells added on every side.  ``src_pos`` / ``sen_pos``: positions (``3 x M`` rows x, y, z, or ``2 x M`` rows z, x) mapped to their nearest
     nodes; ``src_normal``: ``2 x M`` rows ``(nz, nx)``; ``s``: the source table ``T' x M x V`` (host array or tensor).  Returns the record ``Nt x N x V`` (a
@@ -329,7 +360,15 @@ def fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt, PML=20, order=8,
     state arrays (``bsize`` bounds all of them), and ``return_state`` adds ``"e"``: ``V x L x Nx x Nz``.  ``dt`` must respect the unrelaxed speed
     (:func:`loss_model`).  ``loss``: the block given directly in place of ``alpha`` -- a dict with ``mode`` (``"stokes"`` | ``"relax"``), ``g``, ``E`` and the
     interior map ``kap`` (``2 c a``, or ``mud`` under Stokes), as :func:`loss_model` returns it.  ``alpha=None`` and ``loss=None``: the lossless solver,
-    exactly as before."""
+    exactly as before.
+
+    NONLINEARITY.  ``BoA``: a scalar or a ``Z x X`` map of B/A, extended into the PML like ``c``: the density update gains the convective term
+    (``rho + 2 (rz + rx)`` in place of ``rho``; ``convective=False`` switches it off) and the equation of state ``B/2A rn^2 / rho`` (``qdas_fdtd_nonlinear``).  A
+    progressive plane wave then follows Westervelt's equation with ``beta = 1 + B/2A``; ``BoA = 0`` is still nonlinear (``beta = 1``), as in k-Wave.  THE
+    SOURCE TABLE IS IN m/s: a line of sources ``s = v0`` radiates a plane wave of particle velocity ``v0`` (pressure ``rho c v0``) each way, and under
+    nonlinearity its absolute size matters.  ``dt`` is the linear one (the amplitude does not enter the stability check).  There is no shock capturing:
+    without absorption a wave that reaches the shock distance (``sigma = 1``) rings at the grid scale.  ``BoA`` combines with ``alpha`` / ``loss``.
+    ``BoA=None`` or all NaN: the linear solver, exactly as before; a partly NaN map, a negative or an infinite value: ``ValueError``."""
     import torch
     if prec not in ("single", "double"):
         raise DasError("fdtd: prec must be 'single' or 'double'")
@@ -356,6 +395,7 @@ def fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt, PML=20, order=8,
         if loss["speed"] * dt / h > stability_limit(R):
             raise DasError(f"fdtd: with absorption the fastest speed is {loss['speed']:.1f} m/s and c dt / h = {loss['speed'] * dt / h:.4f} is above the "
                            f"stability limit {stability_limit(R):.4f} of order {2 * R}")
+    nl = nl_model(rho, BoA, convective) if rho.shape == c.shape else None
     tab = prepare(c, rho, h, dt, P)
     Nz, Nx = tab["Nz"], tab["Nx"]
     s_host = None if isinstance(s, torch.Tensor) else np.asarray(s, np.float64)
@@ -403,6 +443,9 @@ def fdtd(c, rho, z, x, src_pos, src_normal, s, sen_pos, Nt, dt, PML=20, order=8,
         tb["kap"] = up(np.ascontiguousarray(np.pad(loss["kap"], P, mode="edge").T))
         meta["loss"] = {k: loss[k] for k in ("mode", "L", "y", "tau", "E", "g", "fit_err", "speed")}
         Lm = loss["L"]
+    if nl is not None:                                           # likewise under "bq"
+        tb["bq"] = up(np.ascontiguousarray(np.pad(nl["bq"], P, mode="edge").T))
+        meta["nl"] = dict(convective=nl["convective"], beta_max=nl["beta_max"])
     if prepare_only:
         return meta, tb, s_dev
     rec = torch.empty((Nt, N, V), dtype=rdt, device=dev)
@@ -441,7 +484,8 @@ def launch(meta, tb, st, sb, rec, v0=0, stream=None):
     pulses ``v0 .. v0 + Vb - 1`` are written.  ``stream``: a ``torch.cuda.Stream`` (default: the current one).  Only enqueues.
 
     With ``meta["loss"]`` (``mode``, ``L``, ``g``, ``E``) the call is ``qdas_fdtd_lossy``: ``tb["kap"]`` is the loss map and ``st["e"]`` the memory
-    variables ``Vb x L x Nx x ld`` (relaxation only)."""
+    variables ``Vb x L x Nx x ld`` (relaxation only).  With ``meta["nl"]`` (``convective``) the call is ``qdas_fdtd_nonlinear``, with or without a loss block:
+    ``tb["bq"]`` is the map ``BoA / (2 rho)``."""
     import torch
     dev = st["p"].device
     Vb = int(st["p"].shape[0])
@@ -460,14 +504,15 @@ def launch(meta, tb, st, sb, rec, v0=0, stream=None):
     for k in STATES:
         setattr(a, k, ptr(st[k]))
     for k, t in tb.items():
-        if k != "kap":
+        if k not in ("kap", "bq"):
             setattr(a, k, ptr(t))
     a.s = ptr(sb)
     a.rec = C.c_void_p(rec.data_ptr() + v0 * rec.stride(2) * rec.element_size()) if rec.numel() else None
-    loss = meta.get("loss")
-    if loss is None:
+    loss, nl = meta.get("loss"), meta.get("nl")
+    q = None
+    if loss is None and nl is None:
         _lib.check(_lib.lib().qdas_fdtd(C.byref(d), C.byref(a)))
-    else:
+    elif loss is not None:
         q = _lib.FdtdLoss()
         q.mode, q.L = (_lib.FDTD_LOSS_STOKES if loss["mode"] == "stokes" else _lib.FDTD_LOSS_RELAX), int(loss["L"])
         for k in range(q.L):
@@ -476,6 +521,11 @@ def launch(meta, tb, st, sb, rec, v0=0, stream=None):
         q.e = ptr(st.get("e"))
         if q.L and st.get("e") is not None and (tuple(st["e"].shape[:2]) != (Vb, q.L) or tuple(st["e"].stride()) != (q.L * d.vstride, d.vstride, d.ld, 1)):
             raise DasError(f"fdtd: the memory variables are Vb x L x Nx x ld = {Vb} x {q.L} x {meta['Nx']} x {meta['ld']} in the states' layout")
-        _lib.check(_lib.lib().qdas_fdtd_lossy(C.byref(d), C.byref(a), C.byref(q)))
+        if nl is None:
+            _lib.check(_lib.lib().qdas_fdtd_lossy(C.byref(d), C.byref(a), C.byref(q)))
+    if nl is not None:
+        w = _lib.FdtdNl()
+        w.bq, w.flags = ptr(tb.get("bq")), (0 if nl.get("convective", True) else _lib.FDTD_NL_NO_CONVECTIVE)
+        _lib.check(_lib.lib().qdas_fdtd_nonlinear(C.byref(d), C.byref(a), C.byref(q) if q is not None else None, C.byref(w)))
     if sb.numel():
         sb.record_stream(stream)

@@ -534,7 +534,7 @@ class UltrasoundSystem:
 
     def fdtdSim(self, c, rho=None, cgrd: Scan | None = None, *, waveform, wv_t0, wv_fs, rx_impulse=None, rx_t0=0.0, c0=None, rho0=None, T=None, PML=20,
                 CFL_max=0.25, order=8, isosub=False, field=False, bsize=None, prec="single", ElemMapMethod="nearest", plan_only=False,
-                alpha=None, alpha_power=1.01, alpha_band=None, mechanisms=3):
+                alpha=None, alpha_power=1.01, alpha_band=None, mechanisms=3, BoA=None):
         """``chd = fdtdSim(us, c, rho, cgrd)``: channel data that travelled through the medium ``c``, ``rho`` (``Z x X`` on the Cartesian scan ``cgrd``, by
         default this system's scan), from a 2-D acoustic FDTD solver on the device (``qups_amd/fdtd.py`` -> ``qdas_fdtd``).  It follows the wrapper contract of
         the reference's ``kspaceFirstOrder`` (``src/UltrasoundSystem.m:2458-3170``) -- the time step from ``CFL_max`` as an integer fraction of ``1 / us.fs``
@@ -557,7 +557,15 @@ class UltrasoundSystem:
         of the Fullwave kind, NOT k-Wave's fractional Laplacian; ``y = 2``: k-Wave's ``alpha_mode = 'stokes'``.  The time step respects the unrelaxed speed
         (``fdtd.loss_time_step``), and ``plan["loss"]["fit_err"]`` is the fit's largest relative deviation from the power law inside the band.
         ``alpha=None``: lossless, as before.  ``y`` outside ``[1, 2]`` or a negative ``alpha``: ``ValueError``; a volume with ``alpha``:
-        ``NotImplementedError``.  Not built: absorption in 3-D, nonlinearity, a per-node ``alpha_power``, ``'linear'`` and ``karray-*`` element mapping,
+        ``NotImplementedError``.
+
+        NONLINEARITY (2-D).  ``BoA``: a scalar or a map on ``cgrd`` of B/A (``Medium.BoA``, handed to k-Wave as ``BonA``, ``src/Medium.m:442-447``): k-Wave's
+        nonlinear first-order equations (``qdas_fdtd_nonlinear``), ``beta = 1 + B/2A`` for a plane wave; it combines with ``alpha``.  THE WAVEFORM IS IN m/s
+        then -- the particle velocity at the elements' faces -- and its size matters; ``plan["nl"]`` reports ``beta_max`` and ``mach``, the source Mach number
+        ``max|s| (2 c_max dt / h) / c_min`` of the transmit table.  The time step is the linear one.  There is no shock capturing: without absorption a wave
+        that reaches the shock distance (``sigma = 1``) rings at the grid scale.  ``BoA=None`` or all NaN: linear, as before (the reference drops the field
+        only when every value is NaN); ``BoA = 0`` is still nonlinear (``beta = 1``); a partly NaN map, a negative or an infinite value: ``ValueError``; a
+        volume with ``BoA``: ``NotImplementedError``.  Not built: absorption and nonlinearity in 3-D, shock capturing, a per-node ``alpha_power``, ``'linear'`` and ``karray-*`` element mapping,
         sensor directivity."""
         from . import fdtd as F
         if ElemMapMethod != "nearest":
@@ -572,6 +580,8 @@ class UltrasoundSystem:
         if sum(int(v) > 1 for v in tuple(cgrd.size)) == 3:           # three non-singleton dimensions -> the 3-D solver (reference :2929-2948), as in bfEikonal
             if alpha is not None:
                 raise NotImplementedError("fdtdSim: absorption is built for the 2-D solver only; a volume takes alpha=None")
+            if BoA is not None:
+                raise NotImplementedError("fdtdSim: nonlinearity is built for the 2-D solver only; a volume takes BoA=None")
             return self._fdtdSim3(c, rho, cgrd, waveform=waveform, wv_t0=wv_t0, wv_fs=wv_fs, rx_impulse=rx_impulse, rx_t0=rx_t0, c0=c0, rho0=rho0, T=T, PML=PML,
                                   CFL_max=CFL_max, order=order, isosub=isosub, field=field, bsize=bsize, prec=prec, plan_only=plan_only)
         z, x = cgrd.axes["z"], cgrd.axes["x"]
@@ -609,6 +619,10 @@ class UltrasoundSystem:
         if loss is not None:
             plan["loss"] = loss
             lkw = dict(alpha=alpha, alpha_power=alpha_power, alpha_band=alpha_band, mechanisms=mechanisms)
+        nl = F.nl_model(rho, BoA)
+        if nl is not None:
+            plan["nl"] = dict(beta_max=nl["beta_max"], mach=F.source_mach(s, c, dt, h), bq=nl["bq"])
+            lkw["BoA"] = BoA
         nrm = np.stack([self.tx.normals[2], self.tx.normals[0]])
         V = s.shape[2]
         if field:
